@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- train images/sec of the appearance-flow model (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one pass of the hot path over one batch: forward, loss, hand-scheduled backward,
@@ -9,7 +9,14 @@ A step = one pass of the hot path over one batch: forward, loss, hand-scheduled 
 `appflow_offset`: AppearanceFlowModel, 128x128x3, batch 64 per GPU (weak scaling), synthetic
 car-render-like batches resident in HBM before the timed region, reference initialisers.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the conv / deconv stack -- the kernel family north_star's
+Prints ONE JSON line (rank 0).  A plain run sets up, runs W warm-up steps and EXACTLY K timed steps, and reports the
+headline (`value`, `ms_per_step`, `step_ms`).  `--full` adds what takes runs or launches of its own: the per-kernel
+HIP-event table of the warm-up, events on the conv / deconv family inside the timed region (`roofline`, `stack`,
+`adam`, `hbm_kernels`) and the CPU baseline.  `--dump-outputs DIR` writes, after the timed steps, what the last step
+computed (loss, generated images, updated weights) as DIR/<name>.npy; inputs and initial weights are seeded, so two
+builds can be compared output for output.
+
+With `--full`: `roofline` describes the conv / deconv stack -- the kernel family north_star's
 MFMA target is set on -- as ONE aggregate: algorithmic FLOPs of all its launches (2*N*Ho*Wo*kh*kw*Cin*Cout each,
 DESIGN.md; slab reductions, split-K tails and the filter conversion count with 0 FLOPs but their time) over their
 HIP-event durations measured inside the timed region on the streams they are launched on; `roofline.top_kernel`
@@ -130,6 +137,31 @@ def cpu_baseline(batches=(8, 64), warmup=3, steps=10, budget_s=25.0):
                       % (warmup, steps, budget_s, main_b, batches[0])}
 
 
+DUMP_SAMPLE = 1 << 20       # elements kept of a larger array (the four big fc matrices): 4 MB each
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(model, loss, out_dir):
+    """What the train step hands its caller after the last timed step: the loss, the generated images (model.gen) and
+    every updated weight, float32 (loss: float64).  Arrays above DUMP_SAMPLE elements are reduced to a fixed sample:
+    DUMP_SAMPLE flat indices drawn by np.random.default_rng(0), sorted, the same for every array of that size."""
+    arrays = collections.OrderedDict()
+    arrays['loss'] = np.array([loss], np.float64)
+    arrays['gen'] = model.gen.numpy()
+    for name, v in model.graph.get_variables().items():
+        v = v.astype(np.float32, copy=False)
+        if v.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, v.size, DUMP_SAMPLE))
+            v = v.reshape(-1)[idx]
+        arrays['weight.' + name.replace('/', '.')] = v
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 def self_launch(args):
     """`bench.py --gpus N` from a plain shell: start N ranks (one process per GPU) under torch.distributed.run as fresh
     children -- this process has not touched the GPU -- and exit with their status; rank 0 prints the JSON line."""
@@ -152,17 +184,23 @@ def main():
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=64, help='per-GPU batch (weak scaling)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true', help='do not bracket launches with HIP events')
-    ap.add_argument('--event-every', type=int, default=8, help='steps of the timed region that carry HIP events on the conv/deconv family: every n-th')
-    ap.add_argument('--dump-kernels', action='store_true', help='print the per-kernel table to stderr')
-    ap.add_argument('--dump-ops', action='store_true', help='print every launch of the step in order to stderr')
+    ap.add_argument('--full', action='store_true', help='also measure the per-kernel table, roofline and CPU baseline (off: headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: do not bracket launches with HIP events')
+    ap.add_argument('--event-every', type=int, default=8, help='with --full: steps of the timed region that carry HIP events on the conv/deconv family: every n-th')
+    ap.add_argument('--dump-kernels', action='store_true', help='with --full: print the per-kernel table to stderr')
+    ap.add_argument('--dump-ops', action='store_true', help='with --full: print every launch of the step in order to stderr')
     ap.add_argument('--backend', default='rccl', help="gradient exchange: rccl = RCCL through the C ABI (mv3d_comm_*), nccl = torch.distributed's RCCL binding, "
                                                       "gloo = CPU collectives (rehearsals on one GPU)")
     ap.add_argument('--dp-mode', default='sharded', choices=['sharded', 'allreduce'],
                     help="sharded: reduce-scatter -> Adam on 1/N of every bucket -> all-gather; allreduce: SUM + redundant Adam")
     ap.add_argument('--single-device', action='store_true', help='rehearsal: all ranks share GPU 0')
     args = ap.parse_args()
+    if (args.dump_kernels or args.dump_ops) and not args.full:
+        ap.error('--dump-kernels / --dump-ops need --full (the per-kernel table)')
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -267,7 +305,7 @@ def main():
                 k['bytes'] += by
                 k['ms'] += ms / runs
 
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     # ---- warm-up (untimed).  With kernel timing on, the warm-up steps after the first run the same launches on ONE
     # stream with every launch bracketed by HIP events: that gives the per-kernel table of OWN durations (shares that add
     # up; `stack`, `roofline.alone`).  The timed region then runs the product's multi-stream train step; every
@@ -333,6 +371,8 @@ def main():
         elapsed = float(tt.item())
     loss = float(g.loss_buf[0])
     step_ms = sorted(step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)
 
     # ---- the conv / deconv family inside the timed region (rank 0's GPU)
     kern = collections.OrderedDict()
@@ -355,7 +395,7 @@ def main():
         "dtype": "f32" if (os.environ.get('MV3D_DISABLE') and int(os.environ['MV3D_DISABLE']) & 4096) else "bf16x3",
         "data": "synthetic",
         "value_note": ("all %d timed steps count, including the %d that carry HIP events on every conv / deconv launch (queue barriers: those "
-                       "steps run 10-20 %% slower); --no-kernel-timing gives the undisturbed rate" % (args.steps, n_evsteps)) if timing else "no per-kernel events inside the timed region",
+                       "steps run 10-20 %% slower); a run without --full gives the undisturbed rate" % (args.steps, n_evsteps)) if timing else "no per-kernel events inside the timed region",
         "config": {"workload": "appflow_offset: AppearanceFlowModel 128x128x3, batch %d per GPU, Adam lr 1e-4, "
                                "random-init weights (reference initialisers)" % args.batch,
                    "global_batch": world * args.batch, "parallelism": "dp%d" % world,
@@ -479,7 +519,7 @@ def main():
     out["step_f32_equivalent"] = {"tflops": round(value / world * TRAIN_MFLOP_PER_IMAGE_ALL * 1e6 / 1e12, 2),
                                   "frac_of_f32_mfma_peak": round(value / world * TRAIN_MFLOP_PER_IMAGE_ALL * 1e6 / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
                                   "note": "per GPU; includes fc, Adam and every elementwise kernel in the time"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)
