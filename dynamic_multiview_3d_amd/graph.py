@@ -465,11 +465,19 @@ class TileNode(Node):
 
 
 class ResampleNode(Node):
-    """warp_pts_layer + resample_layer (tf_utils.py:35-42) fused: flow -> (warp_pts, gen)."""
+    """warp_pts_layer + resample_layer (tf_utils.py:35-42) fused: flow -> (warp_pts, gen).  When the source image needs a
+    gradient, the reverse pass scatters it with mv3d_resampler_bwd against the warp the forward pass materialised."""
 
     def __init__(self, src, flow, warp, gen):
         self.src, self.flow, self.warp, self.gen = src, flow, warp, gen
         self.fused_loss = None      # (weight, LossTerm) when gen feeds exactly one plain pixel loss (Graph._fuse_resample_losses)
+
+    def workspace_bytes(self, g):
+        if not self.src.requires_grad:
+            return 0
+        n, h, w, _ = self.flow.shape
+        _, hs, ws, c = self.src.shape
+        return g.lib.resampler_bwd_workspace_bytes(n, h * w, hs, ws, c)
 
     def forward(self, g):
         n, h, w, _ = self.flow.shape
@@ -488,13 +496,48 @@ class ResampleNode(Node):
                                 self.warp.ptr, self.gen.ptr, g.stream)
 
     def backward(self, g):
-        if self.fused_loss is not None or not self.gen.grad_written or not self.flow.requires_grad:
+        if self.fused_loss is not None or not self.gen.grad_written:
             return
         n, h, w, _ = self.flow.shape
         _, hs, ws, c = self.src.shape
-        g.lib.warp_resample_bwd(n, h, w, hs, ws, c, self.src.ptr, self.flow.ptr, self.flow.ld,
-                                self.gen.grad_ptr, self.flow.grad_ptr, self.flow.ld, g.stream)
-        _note_grad_written(self.flow, False)
+        if self.flow.requires_grad:
+            g.lib.warp_resample_bwd(n, h, w, hs, ws, c, self.src.ptr, self.flow.ptr, self.flow.ld,
+                                    self.gen.grad_ptr, self.flow.grad_ptr, self.flow.ld, g.stream)
+            _note_grad_written(self.flow, False)
+        if self.src.requires_grad:
+            g.lib.resampler_bwd(n, h * w, hs, ws, c, self.src.ptr, self.src.ld, self.warp.ptr, 2, self.gen.grad_ptr, self.gen.ld,
+                                None, 0, self.src.grad_ptr, self.src.ld, g.ws_ptr, g.ws_bytes, g.stream)
+            _note_grad_written(self.src, False)
+
+
+class ResamplerNode(Node):
+    """resample_layer / tf.contrib.resampler.resampler(src, warp) with any warp tensor [N, ..., 2] (tf_utils.py:40-42):
+    out [N, ..., C]; gradients w.r.t. the warp and / or the source (mv3d_resampler_*)."""
+
+    def __init__(self, src, warp, out):
+        self.src, self.warp, self.out = src, warp, out
+
+    def _dims(self):
+        n, hs, ws, c = self.src.shape
+        return n, self.warp.rows // n, hs, ws, c
+
+    def workspace_bytes(self, g):
+        return g.lib.resampler_bwd_workspace_bytes(*self._dims()) if self.src.requires_grad else 0
+
+    def forward(self, g):
+        src, warp, out = self.src, self.warp, self.out
+        g.lib.resampler_fwd(*self._dims(), src.ptr, src.ld, warp.ptr, warp.ld, out.ptr, out.ld, g.stream)
+
+    def backward(self, g):
+        src, warp, out = self.src, self.warp, self.out
+        if not out.grad_written or not (warp.requires_grad or src.requires_grad):
+            return
+        g.lib.resampler_bwd(*self._dims(), src.ptr, src.ld, warp.ptr, warp.ld, out.grad_ptr, out.ld,
+                            warp.grad_ptr if warp.requires_grad else None, warp.ld,
+                            src.grad_ptr if src.requires_grad else None, src.ld, g.ws_ptr, g.ws_bytes, g.stream)
+        for t in (warp, src):
+            if t.requires_grad:
+                _note_grad_written(t, False)
 
 
 # =============================================================================================== graph
@@ -669,8 +712,8 @@ class Graph:
             if not isinstance(n, ResampleNode):
                 continue
             n.fused_loss = None
-            if not enabled or self.loss_expr is None:
-                continue
+            if not enabled or self.loss_expr is None or n.src.requires_grad:
+                continue            # the sampled image's gradient has to exist when the source needs one
             gen = n.gen
             uses = [(w, t) for w, t in self.loss_expr.terms if t.a is gen or t.b is gen or t.mask is gen]
             if len(uses) != 1:

@@ -8,7 +8,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 import math
 
 from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, ConvNode, LinearNode, ActNode, ViewNode,
-                    CopyConcatNode, TileNode, ResampleNode, truncated_normal_init, random_normal_init, zeros_init)
+                    CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
 
@@ -154,20 +154,45 @@ def warp_pts_layer(flow_field, name="warp_pts"):
 
 
 def resample_layer(src_img, warp_pts, name="tgt_img"):
-    """tf_utils.py:40-42: tf.contrib.resampler.resampler(src_img, warp_pts)."""
+    """tf_utils.py:40-42: tf.contrib.resampler.resampler(src_img, warp_pts).
+
+    The output of warp_pts_layer over a dense source goes through the fused warp + resampler kernels (ResampleNode; with
+    a source that needs a gradient the reverse pass adds the data gradient).  Any other warp tensor [N, ..., 2] -- a
+    placeholder, a layer's output, a channel slice -- takes the plain resampler (ResamplerNode), whose source may be a
+    channel slice too."""
     g = current_graph()
-    if not isinstance(warp_pts, _WarpPts):
-        raise NotImplementedError("resample_layer expects the output of warp_pts_layer")
-    flow = warp_pts.flow
-    if src_img.requires_grad:
-        raise NotImplementedError("gradient w.r.t. the resampled image (every reference model warps an input image)")
-    if src_img.ld != src_img.C:
-        raise NotImplementedError("resampling a channel-sliced source")
-    n, h, w, _ = flow.shape
-    gen = g.new_tensor((n, h, w, src_img.C), requires_grad=flow.requires_grad, name=name)
-    flow.grad_consumers += 1
-    gen.producer = g.add(ResampleNode(src_img, flow, warp_pts, gen))
-    return gen
+    _check_usable(src_img)
+    if len(src_img.shape) != 4:
+        raise ValueError("resampler: the source must be [N,H,W,C], got %s" % (src_img.shape,))
+    if isinstance(warp_pts, _WarpPts):
+        flow = warp_pts.flow
+        if src_img.ld != src_img.C:
+            raise NotImplementedError("warp_pts_layer over a channel-sliced source")
+        n, h, w, _ = flow.shape
+        if n != src_img.shape[0]:
+            raise ValueError("resampler: batch of the warp (%d) and of the source (%d) differ" % (n, src_img.shape[0]))
+        gen = g.new_tensor((n, h, w, src_img.C), requires_grad=flow.requires_grad or src_img.requires_grad, name=name)
+        flow.grad_consumers += 1
+        if src_img.requires_grad:
+            src_img.grad_consumers += 1
+        gen.producer = g.add(ResampleNode(src_img, flow, warp_pts, gen))
+        return gen
+    _check_usable(warp_pts)
+    if len(warp_pts.shape) < 2 or warp_pts.shape[-1] != 2:
+        raise ValueError("resampler: the warp must be [N, ..., 2], got %s" % (warp_pts.shape,))
+    if warp_pts.shape[0] != src_img.shape[0]:
+        raise ValueError("resampler: batch of the warp (%d) and of the source (%d) differ" % (warp_pts.shape[0], src_img.shape[0]))
+    out = g.new_tensor(warp_pts.shape[:-1] + (src_img.C,), requires_grad=warp_pts.requires_grad or src_img.requires_grad,
+                       name=name)
+    warp_pts.grad_consumers += 1
+    src_img.grad_consumers += 1
+    out.producer = g.add(ResamplerNode(src_img, warp_pts, out))
+    return out
+
+
+def resampler(data, warp, name="resampler"):
+    """tf.contrib.resampler.resampler(data, warp): the same op as resample_layer."""
+    return resample_layer(data, warp, name=name)
 
 
 # ------------------------------------------------------------------------------------------------ layers

@@ -201,6 +201,29 @@ int mv3d_warp_resample_loss(int N, int H, int W, int Hs, int Ws, int C, const vo
                             const void* target, int target_ld, int kind, float weight, void* warp_out, void* gen,
                             void* dflow, int dflow_ld, void* loss_accum, void* stream);
 
+/* ---- the plain resampler: tf.contrib.resampler.resampler(data, warp) for ANY warp (tf_utils.py:40-42) ----------
+ * data [N,Hs,Ws,C] (pixel stride data_ld); warp [N,P,2] (pixel stride warp_ld), P = the product of the warp's middle
+ * dimensions; warp[...,0] is x (column), warp[...,1] is y (row) -- NOT the transposed coords convention of the
+ * mv3d_warp_resample_* entry points above.  out / dout [N,P,C] (pixel strides out_ld / dout_ld).
+ *  - a point is valid iff x > -1 && y > -1 && x < Ws && y < Hs (NaN and +-inf are not); an invalid point gives out 0,
+ *    dwarp 0, and adds nothing to ddata.
+ *  - a tap outside the image reads 0 and its ddata contribution is dropped (never clamped onto a border pixel).
+ *  - same fp32 expressions and operation order as mv3d_warp_resample_fwd / _bwd; dwarp sums the channels in order.
+ * mv3d_resampler_bwd writes dwarp [N,P,2] and/or ddata [N,Hs,Ws,C] (either may be NULL, not both), overwriting them.
+ * ddata is a scatter-add accumulated in 64-bit fixed point (scale 2^k with N*P*max|dout|*2^k <= 2^62): bitwise the same from
+ * run to run; per element it is within (entries at that element) * N*P*max|dout|*2^-63 of the exact sum.  It needs
+ * `workspace` (16-byte aligned) of mv3d_resampler_bwd_workspace_bytes() bytes; a call without ddata needs none.  dout must
+ * be finite for ddata to be defined.
+ * Limits (MV3D_E_UNSUPPORTED): Hs, Ws <= 2^24; N*P and N*Hs*Ws < 2^34; every operand with its stride < 2^40 floats;
+ * N*Hs*Ws*C < 2^37. */
+int mv3d_resampler_fwd(int N, int P, int Hs, int Ws, int C, const void* data, int data_ld,
+                       const void* warp, int warp_ld, void* out, int out_ld, void* stream);
+size_t mv3d_resampler_bwd_workspace_bytes(int N, int P, int Hs, int Ws, int C);
+int mv3d_resampler_bwd(int N, int P, int Hs, int Ws, int C, const void* data, int data_ld,
+                       const void* warp, int warp_ld, const void* dout, int dout_ld,
+                       void* dwarp, int dwarp_ld, void* ddata, int ddata_ld,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- losses: euclidean_loss / l1_loss (tf_utils.py:18-23) -----------------------------------
  * loss_accum[0] += weight * mean_{n,h,w} sum_c f((a-b)*mask);  grad (optional, same shape as a,
  * dense) = d(weight*loss)/da.  kind 2 = squared (euclidean), 1 = absolute (l1).  mask (optional)
