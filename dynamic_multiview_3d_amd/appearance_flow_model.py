@@ -8,7 +8,7 @@ mv3d/nobg_nodm.py:146-150): the reference wires its TFRecord queue into the grap
 that the train driver connects to train_step(**batch), so load_tfrec has no effect on the graph itself.
 """
 from .tf_utils import *                     # noqa: F401,F403  (same star-import as the reference)
-from .model_base import ModelBase, AdamOptimizer
+from .model_base import ModelBase, optimizer_from_conf
 
 
 class AppearanceFlowModel(ModelBase):
@@ -42,7 +42,7 @@ class AppearanceFlowModel(ModelBase):
 
     def build_loss(self):
         self.loss = euclidean_loss(self.gen, self.image1)
-        self.train_op = AdamOptimizer(self.conf['learning_rate']).minimize(self.loss, self.graph)
+        self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def buildModel(self):
         image0 = self.image0

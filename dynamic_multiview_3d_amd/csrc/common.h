@@ -25,6 +25,23 @@ const char* intern_label(const char* fmt, ...) __attribute__((format(printf, 1, 
 bool recording();
 void record(std::function<int(hipStream_t)> fn, const OpInfo& info);
 
+// Optimiser fused into a gradient kernel's epilogue (fc_wgrad_b3_kernel, grad_finalize_kernel): none (store the gradient),
+// TF ApplyAdam, TF ApplyMomentum (Nesterov a uniform run-time flag of the state), TF ApplyGradientDescent.
+enum OptKind { OPT_NONE = 0, OPT_ADAM = 1, OPT_MOMENTUM = 2, OPT_GD = 3 };
+
+// TF ApplyMomentum / ApplyGradientDescent on one element (g already multiplied by the gradient scale), in training_ops' order:
+//   a = a*mu + g;  p -= a*lr   |   p -= g*lr + (a*mu)*lr (Nesterov)   |   p -= g*lr (GD).  No contraction: bit-exact vs numpy.
+__device__ __forceinline__ void momentum_elem(float g, float& p, float& a, float lr, float mu, bool nesterov) {
+#pragma clang fp contract(off)
+    a = a * mu + g;
+    if (nesterov) p = p - (g * lr + (a * mu) * lr);
+    else p = p - a * lr;
+}
+__device__ __forceinline__ void gd_elem(float g, float& p, float lr) {
+#pragma clang fp contract(off)
+    p = p - g * lr;
+}
+
 // Launch now, or append to the plan being recorded on this thread (mv3d_plan_begin).
 // Every dispatch() is exactly ONE kernel launch.
 template <class F>

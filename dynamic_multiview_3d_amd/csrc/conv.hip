@@ -1866,6 +1866,15 @@ int mv3d_fc_wgrad_adam(int B, int in, int out, const void* x, int x_ld, const vo
     if (rc == 1) return fail(MV3D_E_UNSUPPORTED, "mv3d_fc_wgrad_adam: %d x %d x %d is not a layer of the fused kernel (use mv3d_fc_wgrad + mv3d_adam_step_dev)", B, in, out);
     return rc;
 }
+int mv3d_fc_wgrad_sgd(int B, int in, int out, const void* x, int x_ld, const void* dy, int dy_ld, void* M, void* accum, void* db,
+                      const void* sgd_state, void* stream) {
+    if (B <= 0 || in <= 0 || out <= 0 || !x || !dy || !M || !sgd_state || x_ld < in || dy_ld < out)
+        return fail(MV3D_E_INVAL, "mv3d_fc_wgrad_sgd: bad arguments");
+    if (((uintptr_t)M | (uintptr_t)accum) & 15) return fail(MV3D_E_INVAL, "mv3d_fc_wgrad_sgd: M and accum must be 16-byte aligned");
+    int rc = mv3d_fc_wgrad_adam_supported(B, in, out, x_ld, dy_ld) ? try_fc_wgrad_sgd(B, in, out, x, x_ld, dy, dy_ld, M, accum, db, sgd_state, stream, "mv3d_fc_wgrad_sgd") : 1;
+    if (rc == 1) return fail(MV3D_E_UNSUPPORTED, "mv3d_fc_wgrad_sgd: %d x %d x %d is not a layer of the fused kernel (use mv3d_fc_wgrad + mv3d_sgd_step_dev)", B, in, out);
+    return rc;
+}
 int mv3d_fc_wgrad_adam_supported(int B, int in, int out, int x_ld, int dy_ld) {
     if (is_small_fc(B, in, out)) return 0;
     return !(B < 2 || in < 64 || out < 64 || (disabled_paths() & (16 | 4096)) || in % 4 || out % 4 || x_ld % 4 || dy_ld % 4);

@@ -414,6 +414,54 @@ __global__ void adam_advance_kernel(float* st) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st[4] = st[4] * st[1]; st[5] = st[5] * st[2]; }      // beta_power *= beta, in fp32 like TF's update op
 }
 
+// ---------------------------------------------------------------- GD / Momentum (TF ApplyGradientDescent / ApplyMomentum)
+// The counterparts of adam_kernel / adam_dev_kernel: MOM = false is plain gradient descent (loads p, g; stores p = 12 B/param),
+// MOM = true keeps the momentum slot a (20 B/param).  The arithmetic is common.h's momentum_elem / gd_elem.
+template <bool MOM>
+__device__ __forceinline__ void sgd4(float* p, const float* g, float* a, int64_t i, float lr, float mu, bool nesterov, float gscale) {
+    float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+    float4 aa = MOM ? reinterpret_cast<float4*>(a)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* pe = &pp.x; float* ge = &gg.x; float* ae = &aa.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float gk = ge[k] * gscale;
+        if (MOM) momentum_elem(gk, pe[k], ae[k], lr, mu, nesterov);
+        else gd_elem(gk, pe[k], lr);
+    }
+    reinterpret_cast<float4*>(p)[i] = pp;
+    if (MOM) reinterpret_cast<float4*>(a)[i] = aa;
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(int64_t count, float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ a, float lr, float mu, int nesterov, float gscale) {
+    const int64_t nvec = count >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256)
+        sgd4<MOM>(p, g, a, i, lr, mu, nesterov != 0, gscale);
+    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {
+        const int64_t i = (nvec << 2) + threadIdx.x;
+        const float gk = g[i] * gscale;
+        if (MOM) { float pv = p[i], av = a[i]; momentum_elem(gk, pv, av, lr, mu, nesterov != 0); p[i] = pv; a[i] = av; }
+        else { float pv = p[i]; gd_elem(gk, pv, lr); p[i] = pv; }
+    }
+}
+
+// scalars from the device SGD state (MV3D_SGD_*), skipped ranges as adam_dev_kernel
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_dev_kernel(int64_t count, float* __restrict__ p, const float* __restrict__ g,
+                                                     float* __restrict__ a, const float* __restrict__ st, const AdamSkips sk) {
+    const float lr = st[MV3D_SGD_LR], mu = st[MV3D_SGD_MOMENTUM], gscale = st[MV3D_SGD_GSCALE];
+    const bool nesterov = st[MV3D_SGD_NESTEROV] != 0.f;
+    int64_t kept = count >> 2;
+    for (int r = 0; r < sk.n; ++r) kept -= (sk.hi[r] - sk.lo[r]) >> 2;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < kept; j += (int64_t)gridDim.x * 256) {
+        int64_t i = j;
+        for (int r = 0; r < sk.n; ++r)
+            if (i >= (sk.lo[r] >> 2)) i += (sk.hi[r] - sk.lo[r]) >> 2;
+        sgd4<MOM>(p, g, a, i, lr, mu, nesterov, gscale);
+    }
+}
+
 // ---------------------------------------------------------------- gradient finalisation: ONE launch at the end of the reverse pass
 // Every conv / deconv filter gradient leaves its kernel as per-slab partial sums; they used to be summed by one reduce_slabs
 // launch per layer (19 per step on AppearanceFlowModel) and the optimiser then re-read the sums.  Here a table of segments
@@ -428,10 +476,11 @@ struct FinSeg {
     int nslab, vec, blk0, pad;
 };
 
-template <bool ADAM>
+template <int OPT>
 __global__ __launch_bounds__(256) void grad_finalize_kernel(const FinSeg* __restrict__ segs, const int* __restrict__ seg_of_blk,
                                                            const float* __restrict__ G, float* __restrict__ P, float* __restrict__ M,
                                                            float* __restrict__ V, const float* __restrict__ st) {
+    constexpr bool ADAM = OPT == OPT_ADAM, SGD = OPT == OPT_MOMENTUM || OPT == OPT_GD;
     __shared__ float s_sum[4][16][17];
     const FinSeg sg = segs[seg_of_blk[blockIdx.x]];
     const int blk = (int)blockIdx.x - sg.blk0;
@@ -442,6 +491,12 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const FinSeg* __rest
         alpha = lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
         omb1 = 1.0f - b1; omb2 = 1.0f - b2;
     }
+    // Momentum / GD: M is the momentum slot (unused by GD), V unused
+    float lr = 0.f, mu = 0.f;
+    bool nesterov = false;
+    if (SGD) {
+        lr = st[MV3D_SGD_LR]; mu = st[MV3D_SGD_MOMENTUM]; nesterov = st[MV3D_SGD_NESTEROV] != 0.f; gscale = st[MV3D_SGD_GSCALE];
+    }
     auto adam1 = [&](int64_t i, float g) {             // flat index i
         const float gk = g * gscale;
         float m = M[i], v = V[i], pp = P[i];
@@ -450,12 +505,23 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const FinSeg* __rest
         pp -= (m * alpha) / (sqrtf(v) + eps);
         P[i] = pp; M[i] = m; V[i] = v;
     };
+    auto sgd1 = [&](int64_t i, float g) {
+        const float gk = g * gscale;
+        float pp = P[i];
+        if (OPT == OPT_MOMENTUM) { float a = M[i]; momentum_elem(gk, pp, a, lr, mu, nesterov); M[i] = a; }
+        else gd_elem(gk, pp, lr);
+        P[i] = pp;
+    };
     if (sg.nslab == 0) {
         // final gradients: 1024 elements per workgroup, 16 bytes per lane (count is padded to a multiple of 4 by the host)
-        if (!ADAM) return;
+        if (!ADAM && !SGD) return;
         const int64_t i4 = (int64_t)blk * 256 + threadIdx.x;
         if (i4 * 4 >= sg.count) return;
         const int64_t i = (sg.off >> 2) + i4;
+        if constexpr (SGD) {
+            sgd4<OPT == OPT_MOMENTUM>(P, G, M, i, lr, mu, nesterov, gscale);
+            return;
+        }
         float4 pp = reinterpret_cast<float4*>(P)[i], gg = reinterpret_cast<const float4*>(G)[i];
         float4 mm = reinterpret_cast<float4*>(M)[i], vv = reinterpret_cast<float4*>(V)[i];
         float* pe = &pp.x; float* ge = &gg.x; float* me = &mm.x; float* ve = &vv.x;
@@ -473,6 +539,7 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const FinSeg* __rest
     }
     auto fin = [&](int64_t i, float t) {
         if (ADAM) adam1(sg.off + i, t);
+        else if (SGD) sgd1(sg.off + i, t);
         else sg.out[i] = t;
     };
     if (sg.vec) reduce_slabs_body<4>(sg.part, sg.nslab, sg.count, blk, s_sum, fin);
@@ -643,6 +710,23 @@ int mv3d_u8_to_unit_f32(int64_t count, const void* src, void* dst, void* stream)
     });
 }
 
+// skipped ranges of mv3d_adam_step_dev / mv3d_sgd_step_dev: sorted, disjoint, multiple-of-4 sub-ranges of [0, count)
+static int parse_skips(const char* who, int64_t count, int nskip, const int64_t* skip_lo, const int64_t* skip_hi, AdamSkips& sk,
+                       int64_t& skipped) {
+    if (nskip < 0 || nskip > 8 || (nskip > 0 && (!skip_lo || !skip_hi))) return fail(MV3D_E_INVAL, "%s: at most 8 skipped ranges", who);
+    sk = {};
+    sk.n = nskip;
+    skipped = 0;
+    for (int r = 0; r < nskip; ++r) {
+        if ((skip_lo[r] & 3) || (skip_hi[r] & 3) || skip_lo[r] < 0 || skip_hi[r] > count || skip_lo[r] > skip_hi[r])
+            return fail(MV3D_E_INVAL, "%s: skipped range %d is not a multiple-of-4 sub-range", who, r);
+        if (r > 0 && skip_lo[r] < skip_hi[r - 1]) return fail(MV3D_E_INVAL, "%s: skipped ranges must be sorted and disjoint", who);
+        sk.lo[r] = skip_lo[r]; sk.hi[r] = skip_hi[r];
+        skipped += skip_hi[r] - skip_lo[r];
+    }
+    return MV3D_OK;
+}
+
 int mv3d_adam_step(int64_t count, void* p, const void* g, void* m, void* v, float lr, float beta1, float beta2,
                    float eps, float beta1_power, float beta2_power, float grad_scale, void* stream) {
     if (count <= 0 || !p || !g || !m || !v) return fail(MV3D_E_INVAL, "mv3d_adam_step: bad arguments");
@@ -661,17 +745,9 @@ int mv3d_adam_step_dev(int64_t count, void* p, const void* g, void* m, void* v, 
                        const int64_t* skip_hi, void* stream) {
     if (count <= 0 || (count & 3) || !p || !g || !m || !v || !state) return fail(MV3D_E_INVAL, "mv3d_adam_step_dev: bad arguments (count must be a multiple of 4)");
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return fail(MV3D_E_INVAL, "mv3d_adam_step_dev: buffers must be 16-byte aligned");
-    if (nskip < 0 || nskip > 8 || (nskip > 0 && (!skip_lo || !skip_hi))) return fail(MV3D_E_INVAL, "mv3d_adam_step_dev: at most 8 skipped ranges");
-    AdamSkips sk = {};
-    sk.n = nskip;
-    int64_t skipped = 0;
-    for (int r = 0; r < nskip; ++r) {
-        if ((skip_lo[r] & 3) || (skip_hi[r] & 3) || skip_lo[r] < 0 || skip_hi[r] > count || skip_lo[r] > skip_hi[r])
-            return fail(MV3D_E_INVAL, "mv3d_adam_step_dev: skipped range %d is not a multiple-of-4 sub-range", r);
-        if (r > 0 && skip_lo[r] < skip_hi[r - 1]) return fail(MV3D_E_INVAL, "mv3d_adam_step_dev: skipped ranges must be sorted and disjoint");
-        sk.lo[r] = skip_lo[r]; sk.hi[r] = skip_hi[r];
-        skipped += skip_hi[r] - skip_lo[r];
-    }
+    AdamSkips sk;
+    int64_t skipped;
+    if (int rc = parse_skips("mv3d_adam_step_dev", count, nskip, skip_lo, skip_hi, sk, skipped)) return rc;
     const int blocks = (int)std::min<int64_t>(cdiv64((count - skipped) / 4 + 1, 256), 4096);
     return dispatch(stream, OpInfo{"adam", 0.0, 28.0 * (count - skipped)}, [=](hipStream_t s) {
         adam_dev_kernel<<<blocks, 256, 0, s>>>(count, (float*)p, (const float*)g, (float*)m, (float*)v, (const float*)state, sk);
@@ -684,6 +760,38 @@ int mv3d_adam_advance(void* state, void* stream) {
     return dispatch(stream, OpInfo{"adam_advance", 0.0, 16.0}, [=](hipStream_t s) {
         adam_advance_kernel<<<1, 64, 0, s>>>((float*)state);
         return launched("adam_advance_kernel");
+    });
+}
+
+int mv3d_sgd_step(int64_t count, void* p, const void* g, void* accum, float lr, float momentum, int use_nesterov, float grad_scale,
+                  void* stream) {
+    if (count <= 0 || !p || !g) return fail(MV3D_E_INVAL, "mv3d_sgd_step: bad arguments");
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)accum) & 15) return fail(MV3D_E_INVAL, "mv3d_sgd_step: buffers must be 16-byte aligned");
+    if (!accum && (momentum != 0.0f || use_nesterov))
+        return fail(MV3D_E_INVAL, "mv3d_sgd_step: momentum / use_nesterov need the accumulator (accum == NULL is gradient descent)");
+    const bool mom = accum != nullptr;
+    const int nest = use_nesterov ? 1 : 0;
+    const int blocks = (int)std::min<int64_t>(cdiv64(count / 4 + 1, 256), 4096);
+    return dispatch(stream, OpInfo{mom ? "momentum" : "sgd", 0.0, (mom ? 20.0 : 12.0) * count}, [=](hipStream_t s) {
+        if (mom) sgd_kernel<true><<<blocks, 256, 0, s>>>(count, (float*)p, (const float*)g, (float*)accum, lr, momentum, nest, grad_scale);
+        else sgd_kernel<false><<<blocks, 256, 0, s>>>(count, (float*)p, (const float*)g, nullptr, lr, 0.0f, 0, grad_scale);
+        return launched("sgd_kernel");
+    });
+}
+
+int mv3d_sgd_step_dev(int64_t count, void* p, const void* g, void* accum, const void* sgd_state, int nskip, const int64_t* skip_lo,
+                      const int64_t* skip_hi, void* stream) {
+    if (count <= 0 || (count & 3) || !p || !g || !sgd_state) return fail(MV3D_E_INVAL, "mv3d_sgd_step_dev: bad arguments (count must be a multiple of 4)");
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)accum) & 15) return fail(MV3D_E_INVAL, "mv3d_sgd_step_dev: buffers must be 16-byte aligned");
+    AdamSkips sk;
+    int64_t skipped;
+    if (int rc = parse_skips("mv3d_sgd_step_dev", count, nskip, skip_lo, skip_hi, sk, skipped)) return rc;
+    const bool mom = accum != nullptr;
+    const int blocks = (int)std::min<int64_t>(cdiv64((count - skipped) / 4 + 1, 256), 4096);
+    return dispatch(stream, OpInfo{mom ? "momentum" : "sgd", 0.0, (mom ? 20.0 : 12.0) * (count - skipped)}, [=](hipStream_t s) {
+        if (mom) sgd_dev_kernel<true><<<blocks, 256, 0, s>>>(count, (float*)p, (const float*)g, (float*)accum, (const float*)sgd_state, sk);
+        else sgd_dev_kernel<false><<<blocks, 256, 0, s>>>(count, (float*)p, (const float*)g, nullptr, (const float*)sgd_state, sk);
+        return launched("sgd_dev_kernel");
     });
 }
 
@@ -749,15 +857,10 @@ size_t mv3d_grad_finalize_table_bytes(void) {
     for (const FinSegHost& h : *v) blocks += fin_blocks(h);
     return ((v->size() * sizeof(FinSeg) + 255) & ~(size_t)255) + blocks * sizeof(int);
 }
-int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void* params, void* adam_m, void* adam_v,
-                              const void* adam_state, void* stream) {
-    if (!finalize_collecting()) return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: no open collection");
-    const size_t need = mv3d_grad_finalize_table_bytes();
-    std::vector<FinSegHost> segs;
-    finalize_take(&segs);
-    const bool adam = adam_state != nullptr;
-    if (adam && (!grads || !params || !adam_m || !adam_v || (((uintptr_t)grads | (uintptr_t)params | (uintptr_t)adam_m | (uintptr_t)adam_v) & 15)))
-        return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: the optimiser needs the four flat buffers (16-byte aligned)");
+// the body of mv3d_grad_finalize_commit(_sgd): the collection is closed (segs), the arguments are checked
+static int grad_finalize_launch(std::vector<FinSegHost>& segs, size_t need, void* table, size_t table_bytes, void* grads, void* params,
+                                void* slot1, void* slot2, const void* state, int opt, void* stream) {
+    const bool upd = opt != OPT_NONE;           // an optimiser: the segments are placed in the flat buffers
     // one segment per gradient: a range named 'already final' (by the caller, or by a single-slab filter gradient written in place)
     // that a slab segment also produces is the slab segment's, and a range named twice counts once
     std::vector<FinSegHost> keep;
@@ -769,7 +872,7 @@ int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void
             if (h.nslab == 0 && (segs[b].nslab > 0 || b < a)) dup = true;
             if (h.nslab > 0 && segs[b].nslab > 0 && b < a) return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: two filter gradients write the same range");
         }
-        if (!dup && (adam || h.nslab > 0)) keep.push_back(h);
+        if (!dup && (upd || h.nslab > 0)) keep.push_back(h);
     }
     if (keep.empty()) return MV3D_OK;
     const bool dry = !table && recording();      // a plan recorded without a device (host-logic tests): never runs, nothing to upload
@@ -783,7 +886,7 @@ int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void
         d.part = h.part; d.out = h.out; d.count = h.count; d.nslab = h.nslab; d.pad = 0;
         d.vec = h.nslab > 0 && h.count % 4 == 0 && ((uintptr_t)h.part & 15) == 0;
         d.off = 0;
-        if (adam) {
+        if (upd) {
             const int64_t off = h.out - (float*)grads;
             if (off < 0 || (h.nslab == 0 && (off & 3))) return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: segment %zu is not inside the flat gradient buffer", j);
             d.off = off;
@@ -791,7 +894,7 @@ int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void
         d.blk0 = (int)seg_of.size();
         const int nb = fin_blocks(h);
         seg_of.insert(seg_of.end(), nb, (int)j);
-        bytes += 4.0 * h.count * (h.nslab + (adam ? 6 : 1));
+        bytes += 4.0 * h.count * (h.nslab + (opt == OPT_ADAM ? 6 : opt == OPT_MOMENTUM ? 4 : opt == OPT_GD ? 2 : 1));
     }
     const size_t seg_bytes = (dev.size() * sizeof(FinSeg) + 255) & ~(size_t)255;
     // the table is written NOW (record time): a recorded plan replays the launch below against it
@@ -801,11 +904,38 @@ int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void
     const FinSeg* dsegs = (const FinSeg*)table;
     const int* dmap = (const int*)((char*)table + seg_bytes);
     const int blocks = (int)seg_of.size();
-    return dispatch(stream, OpInfo{adam ? "grad_finalize_adam" : "grad_finalize", 0.0, bytes}, [=](hipStream_t s) {
-        if (adam) grad_finalize_kernel<true><<<blocks, 256, 0, s>>>(dsegs, dmap, (const float*)grads, (float*)params, (float*)adam_m, (float*)adam_v, (const float*)adam_state);
-        else grad_finalize_kernel<false><<<blocks, 256, 0, s>>>(dsegs, dmap, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const char* label = opt == OPT_ADAM ? "grad_finalize_adam" : opt == OPT_MOMENTUM ? "grad_finalize_momentum" : opt == OPT_GD ? "grad_finalize_sgd" : "grad_finalize";
+    return dispatch(stream, OpInfo{label, 0.0, bytes}, [=](hipStream_t s) {
+        const float* G = (const float*)grads; float* P = (float*)params; const float* st = (const float*)state;
+        if (opt == OPT_ADAM) grad_finalize_kernel<OPT_ADAM><<<blocks, 256, 0, s>>>(dsegs, dmap, G, P, (float*)slot1, (float*)slot2, st);
+        else if (opt == OPT_MOMENTUM) grad_finalize_kernel<OPT_MOMENTUM><<<blocks, 256, 0, s>>>(dsegs, dmap, G, P, (float*)slot1, nullptr, st);
+        else if (opt == OPT_GD) grad_finalize_kernel<OPT_GD><<<blocks, 256, 0, s>>>(dsegs, dmap, G, P, nullptr, nullptr, st);
+        else grad_finalize_kernel<OPT_NONE><<<blocks, 256, 0, s>>>(dsegs, dmap, nullptr, nullptr, nullptr, nullptr, nullptr);
         return launched("grad_finalize_kernel");
     });
+}
+
+int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void* params, void* adam_m, void* adam_v,
+                              const void* adam_state, void* stream) {
+    if (!finalize_collecting()) return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: no open collection");
+    const size_t need = mv3d_grad_finalize_table_bytes();
+    std::vector<FinSegHost> segs;
+    finalize_take(&segs);
+    const bool adam = adam_state != nullptr;
+    if (adam && (!grads || !params || !adam_m || !adam_v || (((uintptr_t)grads | (uintptr_t)params | (uintptr_t)adam_m | (uintptr_t)adam_v) & 15)))
+        return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit: the optimiser needs the four flat buffers (16-byte aligned)");
+    return grad_finalize_launch(segs, need, table, table_bytes, grads, params, adam_m, adam_v, adam_state, adam ? OPT_ADAM : OPT_NONE, stream);
+}
+
+int mv3d_grad_finalize_commit_sgd(void* table, size_t table_bytes, void* grads, void* params, void* accum, const void* sgd_state,
+                                  void* stream) {
+    if (!finalize_collecting()) return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit_sgd: no open collection");
+    const size_t need = mv3d_grad_finalize_table_bytes();
+    std::vector<FinSegHost> segs;
+    finalize_take(&segs);       // closed whatever follows: a failed commit leaves no collection open (as mv3d_grad_finalize_commit)
+    if (!grads || !params || !sgd_state || (((uintptr_t)grads | (uintptr_t)params | (uintptr_t)accum) & 15))
+        return fail(MV3D_E_INVAL, "mv3d_grad_finalize_commit_sgd: the optimiser needs the flat gradient, parameter (and momentum) buffers, 16-byte aligned, and the state");
+    return grad_finalize_launch(segs, need, table, table_bytes, grads, params, accum, nullptr, sgd_state, accum ? OPT_MOMENTUM : OPT_GD, stream);
 }
 
 }  // extern "C"

@@ -379,7 +379,7 @@ __device__ __forceinline__ uint2 ftr_read(const unsigned char* lds_ptr) {
 // are needed as "8 consecutive batch rows of one column" per lane while the panels arrive row-major, so they
 // are staged as bf16 hi / lo planes [32 b][128 columns] (320-byte rows: 4 consecutive rows x 32 B land on
 // distinct banks) and fetched with the transposing ds_read_b64_tr_b16.
-template <bool ADAM>
+template <int OPT>
 __global__ __launch_bounds__(256) void fc_wgrad_b3_kernel(const FcWgradParams p) {
     constexpr int RS = 320;
     __shared__ __attribute__((aligned(16))) unsigned char xs[2][32 * RS];      // [hi, lo]
@@ -456,7 +456,13 @@ __global__ __launch_bounds__(256) void fc_wgrad_b3_kernel(const FcWgradParams p)
         }
     }
     float alpha = 0.f, omb1 = 0.f, omb2 = 0.f, eps = 0.f, gscale = 1.f;
-    if constexpr (ADAM) {
+    float lr = 0.f, mu = 0.f;
+    bool nesterov = false;
+    if constexpr (OPT == OPT_MOMENTUM || OPT == OPT_GD) {
+        lr = p.state[MV3D_SGD_LR]; mu = p.state[MV3D_SGD_MOMENTUM]; nesterov = p.state[MV3D_SGD_NESTEROV] != 0.f;
+        gscale = p.state[MV3D_SGD_GSCALE];
+    }
+    if constexpr (OPT == OPT_ADAM) {
         const float lr = p.state[0], b1 = p.state[1], b2 = p.state[2], b1p = p.state[4], b2p = p.state[5];
         eps = p.state[3]; gscale = p.state[6];
         {
@@ -470,7 +476,7 @@ __global__ __launch_bounds__(256) void fc_wgrad_b3_kernel(const FcWgradParams p)
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int k = k0 + wt * 64 + t * 32 + li;
-            if constexpr (ADAM) {
+            if constexpr (OPT == OPT_ADAM) {
                 // the gradient never goes to HBM: parameter and slots are read, updated and written back here.  All sixteen rows of
                 // an accumulator tile are requested before the first store (48 loads in flight per lane): vmcnt retires in order and
                 // counts stores, so with four rows per round (round 2's first version) every round paid a load round trip behind the
@@ -494,6 +500,31 @@ __global__ __launch_bounds__(256) void fc_wgrad_b3_kernel(const FcWgradParams p)
                             const int64_t idx = (int64_t)c * p.K + k;
                             p.dW[idx] = pv[r]; p.M1[idx] = mv[r]; p.V2[idx] = vv[r];
                         }
+                    }
+                }
+            } else if constexpr (OPT == OPT_MOMENTUM || OPT == OPT_GD) {
+                // ApplyMomentum reads p and its slot (16 B per parameter with the stores), ApplyGradientDescent p alone (8 B); the
+                // same "every row requested before the first store" order as the Adam epilogue above
+                float pv[16], av[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = c0 + ws * 64 + s * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int64_t idx = (c < p.C && k < p.K) ? (int64_t)c * p.K + k : 0;
+                    pv[r] = p.dW[idx];
+                    if constexpr (OPT == OPT_MOMENTUM) av[r] = p.M1[idx];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (OPT == OPT_MOMENTUM) momentum_elem(acc[s][t][r] * gscale, pv[r], av[r], lr, mu, nesterov);
+                    else gd_elem(acc[s][t][r] * gscale, pv[r], lr);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = c0 + ws * 64 + s * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    if (c < p.C && k < p.K) {
+                        const int64_t idx = (int64_t)c * p.K + k;
+                        p.dW[idx] = pv[r];
+                        if constexpr (OPT == OPT_MOMENTUM) p.M1[idx] = av[r];
                     }
                 }
             } else {
@@ -599,7 +630,7 @@ int try_fc_wgrad(int B, int in, int out, const void* x, int x_ld, const void* dy
     const double flops = 2.0 * B * (double)in * out, bytes = 4.0 * ((double)in * out + (double)B * (in + out));
     const bool b3 = !(disabled_paths() & 4096);
     return dispatch(stream, OpInfo{b3 ? "fc_wgrad_b3" : "fc_wgrad", flops, bytes}, [=](hipStream_t s) {
-        if (b3) fc_wgrad_b3_kernel<false><<<items, 256, 0, s>>>(p);
+        if (b3) fc_wgrad_b3_kernel<OPT_NONE><<<items, 256, 0, s>>>(p);
         else fc_wgrad_kernel<<<items, 256, 0, s>>>(p);
         return launched(who);
     });
@@ -616,7 +647,25 @@ int try_fc_wgrad_adam(int B, int in, int out, const void* x, int x_ld, const voi
     // algorithmic bytes: p, m, v read and written once (24 B per parameter), operands once
     const double flops = 2.0 * B * (double)in * out, bytes = 24.0 * (double)in * out + 4.0 * (double)B * (in + out);
     return dispatch(stream, OpInfo{"fc_wgrad_adam_b3", flops, bytes}, [=](hipStream_t s) {
-        fc_wgrad_b3_kernel<true><<<items, 256, 0, s>>>(p);
+        fc_wgrad_b3_kernel<OPT_ADAM><<<items, 256, 0, s>>>(p);
+        return launched(who);
+    });
+}
+
+// The same with tf.train.MomentumOptimizer's (A != NULL) or tf.train.GradientDescentOptimizer's (A == NULL) update of the
+// matrix: the state is the 8-float SGD record (include/mv3d_hip.h: MV3D_SGD_*)
+int try_fc_wgrad_sgd(int B, int in, int out, const void* x, int x_ld, const void* dy, int dy_ld, void* P, void* A, void* db,
+                     const void* state, void* stream, const char* who) {
+    if (B < 2 || in < 64 || out < 64 || (disabled_paths() & (16 | 4096))) return 1;
+    if (in % 4 || out % 4 || x_ld % 4 || dy_ld % 4 || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dy) & 15)) return 1;
+    FcWgradParams p = {(const float*)x, (const float*)dy, (float*)P, (float*)db, B, in, out, x_ld, dy_ld, cdiv(out, 128), (float*)A, nullptr, (const float*)state};
+    const int items = cdiv(in, 128) * p.ktiles;
+    // algorithmic bytes: p (and a) read and written once (16 / 8 B per parameter), operands once
+    const bool mom = A != nullptr;
+    const double flops = 2.0 * B * (double)in * out, bytes = (mom ? 16.0 : 8.0) * (double)in * out + 4.0 * (double)B * (in + out);
+    return dispatch(stream, OpInfo{mom ? "fc_wgrad_momentum_b3" : "fc_wgrad_sgd_b3", flops, bytes}, [=](hipStream_t s) {
+        if (mom) fc_wgrad_b3_kernel<OPT_MOMENTUM><<<items, 256, 0, s>>>(p);
+        else fc_wgrad_b3_kernel<OPT_GD><<<items, 256, 0, s>>>(p);
         return launched(who);
     });
 }

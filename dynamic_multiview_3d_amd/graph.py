@@ -337,8 +337,13 @@ class LinearNode(Node):
             def emit(g=g, self=self, x=x, y=y, B=B, fin=fin, fout=fout):
                 g.begin_side(60.0, 0.0, cls=2)          # its own stream: 400 MB of HBM traffic must not hold up the conv filter gradients
                 off = 4 * self.m.offset
-                g.lib.fc_wgrad_adam(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr, g.adam_m.data_ptr() + off,
-                                    g.adam_v.data_ptr() + off, self.b.grad_ptr, g.adam_state.data_ptr() + 32, g.stream)
+                if g.optimizer == 'adam':
+                    g.lib.fc_wgrad_adam(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr, g.adam_m.data_ptr() + off,
+                                        g.adam_v.data_ptr() + off, self.b.grad_ptr, g.opt_state.data_ptr() + 32, g.stream)
+                else:                                   # Momentum (slot) or GD (none): mv3d_fc_wgrad_sgd
+                    g.lib.fc_wgrad_sgd(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr,
+                                       g.accum.data_ptr() + off if g.accum is not None else None, self.b.grad_ptr,
+                                       g.opt_state.data_ptr() + 32, g.stream)
                 g.end_side()
             g._deferred.append([g.fcadam_delay, emit])
             g._fused_vars.append(self.m)
@@ -601,8 +606,12 @@ class Graph:
         self._fc_pending = False
         self._pending_idx = 0           # forward launch index the pending event is waited for in front of
         self.plan_bwd_fused = None
-        self.adam_state = None
+        self.opt_state = None
         self.plan_fwd = self.plan_bwd = None
+        # the update rule (model_base: AdamOptimizer, MomentumOptimizer, GradientDescentOptimizer); slots and state follow it
+        self.optimizer = 'adam'
+        self.momentum, self.use_nesterov = 0.0, False
+        self.adam_m = self.adam_v = self.accum = None
         self.beta1, self.beta2, self.eps = 0.9, 0.999, 1e-8
         self.beta1_power = np.float32(self.beta1)
         self.beta2_power = np.float32(self.beta2)
@@ -611,6 +620,13 @@ class Graph:
         self.dp_mode = 'sharded'        # 'sharded': reduce-scatter -> Adam on 1/world of every bucket -> all-gather; 'allreduce': SUM + redundant Adam
         self.comm_stream = None
         self.bucket_elems = 16 * 1024 * 1024        # 64 MB of fp32 gradients per all-reduce bucket
+
+    OPTIMIZERS = ('adam', 'momentum', 'sgd')
+
+    @property
+    def adam_state(self):
+        """The device optimiser state under its original name (an Adam graph's MV3D_ADAM_* records)."""
+        return self.opt_state
 
     def __enter__(self):
         _current.append(self)
@@ -682,9 +698,16 @@ class Graph:
             host[v.offset:v.offset + v.size] = v.init(self.rng, v.shape).reshape(-1)
         self.params = torch.from_numpy(host).to(dev)
         self.grads = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.adam_m = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.adam_v = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.adam_state = torch.zeros(16, dtype=torch.float32, device=dev)     # two records (include/mv3d_hip.h MV3D_ADAM_*): [0:8] main stream, [8:16] the fused fc optimiser's stream
+        # optimiser slots: Adam m and v, one momentum accumulator, or none (gradient descent)
+        if self.optimizer not in self.OPTIMIZERS:
+            raise ValueError("unknown optimizer %r (have %s)" % (self.optimizer, ', '.join(self.OPTIMIZERS)))
+        if self.optimizer == 'adam':
+            self.adam_m = torch.zeros(off, dtype=torch.float32, device=dev)
+            self.adam_v = torch.zeros(off, dtype=torch.float32, device=dev)
+        elif self.optimizer == 'momentum':
+            self.accum = torch.zeros(off, dtype=torch.float32, device=dev)
+        # two records (include/mv3d_hip.h MV3D_ADAM_* / MV3D_SGD_*): [0:8] main stream, [8:16] the fused fc optimiser's stream
+        self.opt_state = torch.zeros(16, dtype=torch.float32, device=dev)
         self.loss_buf = torch.zeros(4, dtype=torch.float32, device=dev)
         self.zero_buf = torch.zeros(1024, dtype=torch.float32, device=dev)
         self.zero_ptr = self.zero_buf.data_ptr()
@@ -972,7 +995,7 @@ class Graph:
                 self._fwd_wait_idx = self._first_fc_hazard()
             else:
                 lib.plan_destroy(plan)
-        self.upload_adam_state()
+        self.upload_optimizer_state()
         return self
 
     def _finalize_commit(self):
@@ -985,8 +1008,14 @@ class Graph:
         self._fin_tables.append(table)
         self.begin_side(20.0, 0.0)
         try:
-            lib.grad_finalize_commit(table.data_ptr() if on_gpu else None, tb, self.grads.data_ptr(), self.params.data_ptr(),
-                                     self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.adam_state.data_ptr(), self.stream)
+            tp = table.data_ptr() if on_gpu else None
+            if self.optimizer == 'adam':
+                lib.grad_finalize_commit(tp, tb, self.grads.data_ptr(), self.params.data_ptr(),
+                                         self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.opt_state.data_ptr(), self.stream)
+            else:
+                lib.grad_finalize_commit_sgd(tp, tb, self.grads.data_ptr(), self.params.data_ptr(),
+                                             self.accum.data_ptr() if self.accum is not None else None, self.opt_state.data_ptr(),
+                                             self.stream)
         finally:
             self.end_side()
         self._fin_done |= {id(v) for v in self._fin_vars}
@@ -1060,7 +1089,7 @@ class Graph:
             torch.cuda.current_stream(self.device).wait_event(self._fc_event)
             self._fc_pending = False
 
-    settle = _settle        # public name: call before touching Graph.params / adam_m / adam_v / grads directly
+    settle = _settle        # public name: call before touching Graph.params / adam_m / adam_v / accum / grads directly
 
     def run_forward(self):
         st = self._stream_ptr()
@@ -1112,34 +1141,53 @@ class Graph:
         if self.world_size > 1:
             self.comm.allreduce_sum_(self.grads, 0, self.flat_size, self._stream_ptr())
 
-    def upload_adam_state(self):
-        """lr, betas, epsilon, the two beta powers and the gradient scale (1 / world size) to the device Adam state."""
-        if self.adam_state is None or self.lr is None:
+    def upload_optimizer_state(self):
+        """The device optimiser state: Adam's lr, betas, epsilon and the two beta powers, or Momentum / GD's lr, momentum and
+        Nesterov flag; then the gradient scale (1 / world size)."""
+        if self.opt_state is None or self.lr is None:
             return
-        vals = np.array([self.lr, self.beta1, self.beta2, self.eps, self.beta1_power, self.beta2_power, 1.0 / self.world_size, 0.0], np.float32)
+        if self.optimizer == 'adam':
+            vals = [self.lr, self.beta1, self.beta2, self.eps, self.beta1_power, self.beta2_power]
+        else:
+            vals = [self.lr, self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0, 0.0, 0.0]
+        vals = np.array(vals + [1.0 / self.world_size, 0.0], np.float32)
         self._settle()
-        self.adam_state.copy_(torch.from_numpy(np.concatenate([vals, vals])))
+        self.opt_state.copy_(torch.from_numpy(np.concatenate([vals, vals])))
 
-    def _adam_range(self, lo, hi, stream, skips=None, state=None):
+    upload_adam_state = upload_optimizer_state
+
+    def _opt_range(self, lo, hi, stream, skips=None, state=None):
+        """The optimiser over the flat range [lo, hi) (minus `skips`): mv3d_adam_step_dev or mv3d_sgd_step_dev."""
         off = lo * 4
         n, slo, shi = (0, None, None) if skips is None else skips
-        self.lib.adam_step_dev(hi - lo, self.params.data_ptr() + off, self.grads.data_ptr() + off, self.adam_m.data_ptr() + off,
-                               self.adam_v.data_ptr() + off, self.adam_state.data_ptr() if state is None else state, n, slo, shi, stream)
+        state = self.opt_state.data_ptr() if state is None else state
+        if self.optimizer == 'adam':
+            self.lib.adam_step_dev(hi - lo, self.params.data_ptr() + off, self.grads.data_ptr() + off, self.adam_m.data_ptr() + off,
+                                   self.adam_v.data_ptr() + off, state, n, slo, shi, stream)
+        else:
+            self.lib.sgd_step_dev(hi - lo, self.params.data_ptr() + off, self.grads.data_ptr() + off,
+                                  self.accum.data_ptr() + off if self.accum is not None else None, state, n, slo, shi, stream)
+
+    _adam_range = _opt_range
 
     def _adam_advance(self, stream=None, both=True):
         """beta powers *= betas: on the device (behind every optimiser launch of this step) and in the host mirror the
-        checkpoints read"""
+        checkpoints read.  Momentum and GD have nothing to advance."""
+        if self.optimizer != 'adam':
+            return
         st = self._stream_ptr() if stream is None else stream
-        self.lib.adam_advance(self.adam_state.data_ptr(), st)
+        self.lib.adam_advance(self.opt_state.data_ptr(), st)
         if both:                                             # the fused fc optimiser's record (advanced on its own stream by run_backward_fused)
-            self.lib.adam_advance(self.adam_state.data_ptr() + 32, st)
+            self.lib.adam_advance(self.opt_state.data_ptr() + 32, st)
         self.beta1_power = np.float32(self.beta1_power * np.float32(self.beta1))
         self.beta2_power = np.float32(self.beta2_power * np.float32(self.beta2))
 
-    def apply_adam(self):
+    def apply_optimizer(self):
         self._settle()
-        self._adam_range(0, self.flat_size, self._stream_ptr())
+        self._opt_range(0, self.flat_size, self._stream_ptr())
         self._adam_advance()
+
+    apply_adam = apply_optimizer
 
     def run_backward_fused(self):
         """Single-GPU reverse pass with the fc matrices' optimiser inside their filter-gradient kernels; one small launch
@@ -1149,7 +1197,7 @@ class Graph:
         pipelined = self.pipeline_fc and ns >= 2 and self._fwd_wait_idx is not None
         self.lib.plan_run_range_multi(self.plan_bwd_fused, 0, self.n_launch_bwd_fused, st, sides, ns,
                                       (1 if pipelined else 0) | (2 if pipelined and self.fc_after_wgrads else 0))
-        fc_state = self.adam_state.data_ptr() + 32
+        fc_state = self.opt_state.data_ptr() + 32
         if pipelined and self.fc_after_wgrads:
             # flags bit 2 made the plan hold the class-2 launches back: issue them now, behind the conv filter gradients
             for k, q in enumerate(self.side_streams):
@@ -1166,16 +1214,17 @@ class Graph:
         else:
             fc_stream = st
         lo, hi = self._bias_span
-        self._adam_range(lo, hi, fc_stream, self._bias_skip, state=fc_state)
-        self.lib.adam_advance(fc_state, fc_stream)
+        self._opt_range(lo, hi, fc_stream, self._bias_skip, state=fc_state)
+        if self.optimizer == 'adam':
+            self.lib.adam_advance(fc_state, fc_stream)
         if pipelined:
             if self._fc_event is None:
                 self._fc_event = torch.cuda.Event()
             self._fc_event.record(fcq)
             self._fc_pending = True
             self._pending_idx = self._fwd_wait_idx
-        if not self._finalized_in_plan:          # otherwise the plan's last launch (grad_finalize_adam) was the optimiser of everything else
-            self._adam_range(0, self.flat_size, st, (len(self._skip_lo), self._skip_lo, self._skip_hi))
+        if not self._finalized_in_plan:          # otherwise the plan's last launch (grad_finalize_<kind>) was the optimiser of everything else
+            self._opt_range(0, self.flat_size, st, (len(self._skip_lo), self._skip_lo, self._skip_hi))
         self._adam_advance(st, both=False)
 
     def run_backward_with_adam(self):
@@ -1205,7 +1254,7 @@ class Graph:
                 if self.adam_timing is not None:      # bench: HIP events around the optimiser launches, on their stream
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(self.adam_stream)
-                self._adam_range(plo, phi, self.adam_stream.cuda_stream)
+                self._opt_range(plo, phi, self.adam_stream.cuda_stream)
                 if self.adam_timing is not None:
                     e1.record(self.adam_stream)
                     self.adam_timing.append((e0, e1))
@@ -1214,6 +1263,8 @@ class Graph:
         for st in (self.side_streams or []):
             main.wait_stream(st)
         self._adam_advance(main.cuda_stream)
+
+    run_backward_with_optimizer = run_backward_with_adam
 
     def run_backward_overlapped(self, with_adam=False):
         """Data-parallel reverse pass.  The recorded backward sequence is issued in segments; after each segment the gradients
@@ -1254,8 +1305,8 @@ class Graph:
                 assert n * W == hi - lo and n % 4 == 0, "bucket not divisible by 4 * world"
                 comm.reduce_scatter_sum_(self.grads, lo, n, cs)
                 a = lo + comm.rank * n
-                self._adam_range(a, a + n, cs)
-                self._slots_sharded = True      # this rank's Adam slots are now current on its own slices only
+                self._opt_range(a, a + n, cs)
+                self._slots_sharded = bool(self._slots())      # this rank's optimiser slots are now current on its own slices only
                 # the updated slices of a bucket whose parameters the next forward pass reads late (the fc matrices: 97 % of the
                 # bytes) are gathered AFTER every bucket has been reduced and, on the GPU, under the next step's encoder
                 use = self._bucket_first_use[self.grad_buckets.index((end, lo, hi))]
@@ -1266,7 +1317,7 @@ class Graph:
             else:
                 comm.allreduce_sum_(self.grads, lo, hi - lo, cs)
                 if with_adam:
-                    self._adam_range(lo, hi, cs)
+                    self._opt_range(lo, hi, cs)
             if on_gpu:
                 ctx.__exit__(None, None, None)
         if on_gpu:
@@ -1292,7 +1343,7 @@ class Graph:
             self._adam_advance()
 
     def train_step(self):
-        """forward + loss + reverse pass + (all-reduce) + Adam; returns the device loss scalar."""
+        """forward + loss + reverse pass + (all-reduce) + optimiser; returns the device loss scalar."""
         self.run_forward()
         if self.world_size > 1:
             self.run_backward_overlapped(with_adam=True)
@@ -1302,7 +1353,7 @@ class Graph:
             self.run_backward_with_adam()
         else:
             self.run_backward()
-            self.apply_adam()
+            self.apply_optimizer()
         return self.loss_buf[0]
 
     # ---------------------------------------------------------------- variables I/O
@@ -1319,8 +1370,17 @@ class Graph:
         self._settle()
         return OrderedDict((k, v.grad_value().detach().cpu().numpy().copy()) for k, v in self.variables.items() if v.has_grad)
 
+    def _slots(self):
+        """[(TF slot name, flat buffer)] of the active optimiser: tf.train.AdamOptimizer's 'Adam' (m) and 'Adam_1' (v),
+        tf.train.MomentumOptimizer's 'Momentum', none for tf.train.GradientDescentOptimizer."""
+        if self.optimizer == 'adam':
+            return [('Adam', self.adam_m), ('Adam_1', self.adam_v)]
+        if self.optimizer == 'momentum':
+            return [('Momentum', self.accum)]
+        return []
+
     def gather_optimizer_state(self):
-        """COLLECTIVE (every rank calls it): after sharded data-parallel steps a rank's Adam slots are current only on its own
+        """COLLECTIVE (every rank calls it): after sharded data-parallel steps a rank's optimiser slots are current only on its own
         1/world slice of every bucket; all-gather them (same lo / n layout as the parameters) so that any rank can write a
         complete checkpoint.  No-op on one GPU and in 'allreduce' mode."""
         self._settle()
@@ -1334,48 +1394,55 @@ class Graph:
         for _, lo, hi in self.grad_buckets:
             if hi > lo:
                 n = (hi - lo) // W
-                self.comm.allgather_(self.adam_m, lo, n, cs)
-                self.comm.allgather_(self.adam_v, lo, n, cs)
+                for _, buf in self._slots():
+                    self.comm.allgather_(buf, lo, n, cs)
         if on_gpu:
             torch.cuda.synchronize(self.device)
         self._slots_sharded = False
 
     def state_dict(self):
-        """TF-Saver-style names: <var>, <var>/Adam, <var>/Adam_1, beta1_power, beta2_power
-        (train.py:70-71 saves GLOBAL_VARIABLES)."""
+        """TF-Saver-style names: <var> and the active optimiser's slots -- <var>/Adam, <var>/Adam_1, beta1_power, beta2_power
+        (Adam), <var>/Momentum (Momentum), nothing else (GD) -- (train.py:70-71 saves GLOBAL_VARIABLES)."""
         self._settle()
         if self.world_size > 1 and getattr(self, '_slots_sharded', False):
-            raise RuntimeError("sharded data-parallel step: this rank holds 1/%d of the Adam slots; call "
+            raise RuntimeError("sharded data-parallel step: this rank holds 1/%d of the optimiser slots; call "
                                "Graph.gather_optimizer_state() on EVERY rank before state_dict() / Saver.save()" % self.world_size)
         sd = OrderedDict()
+        slots = self._slots()
         for k, v in self.variables.items():
             sd[k] = v.value().detach().cpu().clone()
             if v.has_grad:
-                sd[k + '/Adam'] = self.adam_m[v.offset:v.offset + v.size].view(v.shape).detach().cpu().clone()
-                sd[k + '/Adam_1'] = self.adam_v[v.offset:v.offset + v.size].view(v.shape).detach().cpu().clone()
-        sd['beta1_power'] = torch.tensor(float(self.beta1_power))
-        sd['beta2_power'] = torch.tensor(float(self.beta2_power))
+                for name, buf in slots:
+                    sd[k + '/' + name] = buf[v.offset:v.offset + v.size].view(v.shape).detach().cpu().clone()
+        if self.optimizer == 'adam':
+            sd['beta1_power'] = torch.tensor(float(self.beta1_power))
+            sd['beta2_power'] = torch.tensor(float(self.beta2_power))
         return sd
 
     def load_state_dict(self, sd):
         self._settle()
+        slots = self._slots()
+        names = {n for n, _ in slots}
         missing = [k for k in self.variables if k not in sd]
-        slots = {'beta1_power', 'beta2_power'}
-        unexpected = [k for k in sd if k not in slots and k not in self.variables and
-                      not (k.rsplit('/', 1)[0] in self.variables and k.rsplit('/', 1)[-1] in ('Adam', 'Adam_1'))]
+        if self.optimizer == 'momentum':        # the accumulator is what identifies a Momentum checkpoint (Adam's: the beta powers)
+            missing += [k + '/Momentum' for k, v in self.variables.items() if v.has_grad and k + '/Momentum' not in sd]
+        scalars = {'beta1_power', 'beta2_power'} if self.optimizer == 'adam' else set()
+        unexpected = [k for k in sd if k not in scalars and k not in self.variables and
+                      not (k.rsplit('/', 1)[0] in self.variables and k.rsplit('/', 1)[-1] in names)]
         bad = [k for k, v in self.variables.items() if k in sd and tuple(sd[k].shape) != tuple(v.shape)]
-        if missing or unexpected or bad or not slots <= set(sd):
-            raise KeyError("checkpoint does not match the model: missing %s; unexpected %s; shape mismatch %s%s"
-                           % (missing[:8], unexpected[:8], [(k, tuple(sd[k].shape), self.variables[k].shape) for k in bad[:8]],
-                              '' if slots <= set(sd) else '; no beta1_power / beta2_power'))
+        if missing or unexpected or bad or not scalars <= set(sd):
+            raise KeyError("checkpoint does not match the model (%s optimizer): missing %s; unexpected %s; shape mismatch %s%s"
+                           % (self.optimizer, missing[:8], unexpected[:8], [(k, tuple(sd[k].shape), self.variables[k].shape) for k in bad[:8]],
+                              '' if scalars <= set(sd) else '; no beta1_power / beta2_power'))
         for k, v in self.variables.items():
             v.value().copy_(sd[k])
-            if k + '/Adam' in sd:
-                self.adam_m[v.offset:v.offset + v.size].view(v.shape).copy_(sd[k + '/Adam'])
-                self.adam_v[v.offset:v.offset + v.size].view(v.shape).copy_(sd[k + '/Adam_1'])
-        self.beta1_power = np.float32(float(sd['beta1_power']))
-        self.beta2_power = np.float32(float(sd['beta2_power']))
-        self.upload_adam_state()
+            for name, buf in slots:
+                if k + '/' + name in sd:
+                    buf[v.offset:v.offset + v.size].view(v.shape).copy_(sd[k + '/' + name])
+        if self.optimizer == 'adam':
+            self.beta1_power = np.float32(float(sd['beta1_power']))
+            self.beta2_power = np.float32(float(sd['beta2_power']))
+        self.upload_optimizer_state()
 
 
 # =============================================================================================== initialisers

@@ -7,7 +7,7 @@ Deviation: the reference hard-codes self.batch_size = 64 (main_model.py:19) whil
 conf['batch_size'] (main_model.py:47-50); here conf['batch_size'] is used throughout.
 """
 from .tf_utils import *                     # noqa: F401,F403
-from .model_base import ModelBase, AdamOptimizer
+from .model_base import ModelBase, optimizer_from_conf
 
 
 class Base_Prediction_Model(ModelBase):
@@ -109,7 +109,7 @@ class Base_Prediction_Model(ModelBase):
             self.loss += euclidean_loss(self.gen_image1, self.image1)
         if 'use_depth' in self.conf:
             self.loss += euclidean_loss(self.gen_dimage1, self.dimage1) * self.conf['depth_lr_factor']
-        self.train_op = AdamOptimizer(self.conf['learning_rate']).minimize(self.loss, self.graph)
+        self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def visualize(self, sess=None, **feeds):
         """One forward pass, then the reference's qualitative outputs (visualize.py)."""

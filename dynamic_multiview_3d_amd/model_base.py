@@ -16,8 +16,8 @@ from .graph import Graph
 
 
 class Saver:
-    """tf.train.Saver stand-in (train.py:70-71,134-136; mv3d/utils/tf_utils.py:199-212): variables + Adam slots +
-    beta powers under their TF names, written as a TensorFlow V2 checkpoint (`<prefix>.index`,
+    """tf.train.Saver stand-in (train.py:70-71,134-136; mv3d/utils/tf_utils.py:199-212): variables + the optimiser's slots
+    (Adam: m, v and the beta powers; Momentum: the accumulator; GD: none) under their TF names, written as a TensorFlow V2 checkpoint (`<prefix>.index`,
     `<prefix>.data-00000-of-00001`, and the `checkpoint` state file next to them) -- see tf_checkpoint.py."""
 
     def __init__(self, graph):
@@ -50,8 +50,54 @@ class AdamOptimizer:
     def minimize(self, loss, graph):
         graph.loss_expr = loss
         graph.lr = self.lr
+        graph.optimizer = 'adam'
         graph.beta1, graph.beta2, graph.eps = self.beta1, self.beta2, self.eps
         return 'train_op'
+
+
+class GradientDescentOptimizer:
+    """tf.train.GradientDescentOptimizer(lr).minimize(loss): ApplyGradientDescent, p -= g*lr (mv3d_sgd_step); no slots."""
+
+    def __init__(self, learning_rate):
+        self.lr = learning_rate
+
+    def minimize(self, loss, graph):
+        graph.loss_expr = loss
+        graph.lr = self.lr
+        graph.optimizer = 'sgd'
+        graph.momentum, graph.use_nesterov = 0.0, False
+        return 'train_op'
+
+
+class MomentumOptimizer:
+    """tf.train.MomentumOptimizer(lr, momentum, use_nesterov=False).minimize(loss): ApplyMomentum (mv3d_sgd_step with the
+    accumulator); one slot, <var>/Momentum."""
+
+    def __init__(self, learning_rate, momentum, use_nesterov=False):
+        self.lr, self.momentum, self.use_nesterov = learning_rate, momentum, bool(use_nesterov)
+
+    def minimize(self, loss, graph):
+        graph.loss_expr = loss
+        graph.lr = self.lr
+        graph.optimizer = 'momentum'
+        graph.momentum, graph.use_nesterov = self.momentum, self.use_nesterov
+        return 'train_op'
+
+
+def optimizer_from_conf(conf, learning_rate, **adam_kw):
+    """The optimiser a configuration asks for: conf['optimizer'] in {'adam' (default when absent), 'momentum', 'sgd'};
+    'momentum' needs conf['momentum'] (TF has no default) and takes conf['use_nesterov'] (default False).  adam_kw: the model's
+    own AdamOptimizer arguments.  Raises ValueError on anything else, before any device work."""
+    name = conf.get('optimizer', 'adam')
+    if name == 'adam':
+        return AdamOptimizer(learning_rate, **adam_kw)
+    if name == 'sgd':
+        return GradientDescentOptimizer(learning_rate)
+    if name == 'momentum':
+        if conf.get('momentum') is None:
+            raise ValueError("conf['optimizer'] = 'momentum' needs conf['momentum']")
+        return MomentumOptimizer(learning_rate, float(conf['momentum']), bool(conf.get('use_nesterov', False)))
+    raise ValueError("unknown conf['optimizer'] %r (have 'adam', 'momentum', 'sgd')" % (name,))
 
 
 class ModelBase(object):
@@ -100,7 +146,7 @@ class ModelBase(object):
         g.comm = comm if comm is not None else TorchComm(group)
         if mode is not None:
             g.dp_mode = mode
-        g.upload_adam_state()          # gradient scale 1 / world size for the SUM
+        g.upload_optimizer_state()     # gradient scale 1 / world size for the SUM
 
 
 def iteration_from_checkpoint_name(path):

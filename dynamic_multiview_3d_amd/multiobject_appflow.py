@@ -8,7 +8,7 @@ masked_image_loss.  The 13 reader tensors (multiobject_appflow.py:31-43) are fed
 'fully_conv' (the fc path reshapes to 4096) -- BASELINE config 5 is the 256x256 extrapolation.
 """
 from .tf_utils import *                     # noqa: F401,F403
-from .model_base import ModelBase, AdamOptimizer
+from .model_base import ModelBase, optimizer_from_conf
 
 INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3), ('image1_only0', 3),
           ('image1_only1', 3), ('image1_mask0', 1), ('image1_mask1', 1), ('depth0', 1), ('depth1', 1),
@@ -193,7 +193,7 @@ class MultiObjectAppFlow(ModelBase):
             mask_loss += euclidean_loss(self.gen_image1_mask1, self.image1_mask1) * mask_factor
             self.loss += mask_loss
 
-        self.train_op = AdamOptimizer(self.conf['learning_rate']).minimize(self.loss, self.graph)
+        self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def visualize(self, sess=None, **feeds):
         """One forward pass, then the reference's qualitative outputs (visualize.py)."""

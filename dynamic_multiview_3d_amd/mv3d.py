@@ -11,7 +11,7 @@ No new kernels: the tf.slice pairs become channel views, the mask product and th
 loss kernel (mv3d_pixel_loss_strided).
 """
 from .tf_utils import *                     # noqa: F401,F403
-from .model_base import ModelBase, AdamOptimizer
+from .model_base import ModelBase, optimizer_from_conf
 
 
 class _MV3DBase(ModelBase):
@@ -86,7 +86,7 @@ class _MV3DBase(ModelBase):
         raise NotImplementedError
 
     def _minimize(self):
-        self.train_op = AdamOptimizer(self.learning_rate).minimize(self.loss, self.graph)
+        self.train_op = optimizer_from_conf(self.conf, self.learning_rate, beta1=0.9).minimize(self.loss, self.graph)
 
 
 class mv3d_nobg_nodm(_MV3DBase):

@@ -269,6 +269,23 @@ int mv3d_fc_wgrad_adam(int B, int in, int out, const void* x, int x_ld, const vo
                        void* db, const void* adam_state, void* stream);
 int mv3d_fc_wgrad_adam_supported(int B, int in, int out, int x_ld, int dy_ld);
 
+/* ---- GD / Momentum: tf.train.GradientDescentOptimizer (ApplyGradientDescent) and tf.train.MomentumOptimizer (ApplyMomentum) ----
+ * g *= grad_scale first, then in TF's order (fp32, no contraction):
+ *   accum == NULL:  p -= g*lr                                          (momentum must be 0 and use_nesterov 0)
+ *   accum != NULL:  a = a*mu + g;  p -= a*lr   |   p -= g*lr + (a*mu)*lr  (use_nesterov)
+ * 12 (GD) / 20 (Momentum) B per parameter.  Neither optimiser has a per-step "advance". */
+int mv3d_sgd_step(int64_t count, void* p, const void* g, void* accum, float lr, float momentum, int use_nesterov,
+                  float grad_scale, void* stream);
+/* Device state of the same 8-float record size and GSCALE index as the Adam state (nesterov: 0.0f or 1.0f); _dev reads the scalars
+ * from it and leaves up to 8 index ranges untouched, as mv3d_adam_step_dev. */
+enum { MV3D_SGD_LR = 0, MV3D_SGD_MOMENTUM = 1, MV3D_SGD_NESTEROV = 2, MV3D_SGD_GSCALE = 6, MV3D_SGD_STATE_FLOATS = 8 };
+int mv3d_sgd_step_dev(int64_t count, void* p, const void* g, void* accum, const void* sgd_state, int nskip,
+                      const int64_t* skip_lo, const int64_t* skip_hi, void* stream);
+/* mv3d_fc_wgrad_adam with the Momentum (accum != NULL) or GD (accum == NULL) update of M fused into the epilogue (16 / 8 B of HBM
+ * traffic per parameter); the layer set is mv3d_fc_wgrad_adam_supported's. */
+int mv3d_fc_wgrad_sgd(int B, int in, int out, const void* x, int x_ld, const void* dy, int dy_ld, void* M, void* accum,
+                      void* db, const void* sgd_state, void* stream);
+
 /* ---- gradient finalisation: the slab reductions of ALL filter gradients (+ their optimiser update) in one launch ------------
  * Replaces, on the recorded single-GPU step, the per-layer partial-filter reductions behind tf.gradients' Conv2DBackpropFilter
  * ops and the tf.train.AdamOptimizer ApplyAdam ops of every variable that is not an fc matrix (appearance_flow_model.py:77).
@@ -288,6 +305,10 @@ int mv3d_grad_finalize_add(void* grad, int64_t count);
 size_t mv3d_grad_finalize_table_bytes(void);
 int mv3d_grad_finalize_commit(void* table, size_t table_bytes, void* grads, void* params, void* adam_m, void* adam_v,
                               const void* adam_state, void* stream);
+/* _commit with ApplyMomentum (accum != NULL) or ApplyGradientDescent (accum == NULL) in place of ApplyAdam (mv3d_sgd_step_dev's
+ * arithmetic, same bits); sgd_state is required (gradients only: mv3d_grad_finalize_commit with adam_state NULL). */
+int mv3d_grad_finalize_commit_sgd(void* table, size_t table_bytes, void* grads, void* params, void* accum, const void* sgd_state,
+                                  void* stream);
 int mv3d_grad_finalize_abort(void);
 
 /* ---- data-parallel exchange: RCCL over xGMI behind the ABI (one process per GPU) -----------------------------------------
