@@ -16,7 +16,7 @@ struct PlanOp {
     double total_ms;
     int runs;
     bool selected = true;      // bracketed with events when profiling
-    int side = 0;              // 1: may run on the side stream of mv3d_plan_run_range2 (see mv3d_plan_side)
+    int side = 0;              // k > 0: side work of class k (see mv3d_plan_side)
 };
 
 struct mv3d_plan {
@@ -103,8 +103,9 @@ int mv3d_plan_begin(mv3d_plan* p) {
     mv3d::g_side = 0;
     return MV3D_OK;
 }
-// Launches recorded after mv3d_plan_side(1) (until mv3d_plan_side(0)) are tagged as side work: they depend on
-// everything recorded before them, and nothing recorded later in the same plan range depends on them.
+// Launches recorded after mv3d_plan_side(k > 0) (until mv3d_plan_side(0)) are tagged as side work of class k: they depend on
+// everything recorded before them, nothing recorded later in the same plan range depends on them, and they share no scratch
+// with main work (nor with classes on other streams).
 int mv3d_plan_side(int side) {
     if (side < 0 || side > MV3D_MAX_SIDE) return mv3d::fail(MV3D_E_INVAL, "mv3d_plan_side: side %d not in [0, %d]", side, MV3D_MAX_SIDE);
     mv3d::g_side = side;
@@ -124,13 +125,8 @@ int mv3d_plan_run_range(mv3d_plan* p, int begin, int end, void* stream) {
     return mv3d_plan_run_range_multi(p, begin, end, stream, nullptr, 0, 0);
 }
 
-int mv3d_plan_run_range2(mv3d_plan* p, int begin, int end, void* stream, void* side_stream) {
-    void* sides[1] = {side_stream};
-    return mv3d_plan_run_range_multi(p, begin, end, stream, sides, side_stream ? 1 : 0, 0);
-}
-
-// Multi-stream form: launches tagged side k (1..nside) go to side_streams[(k-1) % nside] behind an event on `stream`
-// (fork whenever a side's run of launches begins), `stream` waits for every used side stream at the end of the range.
+// Multi-stream form: launches tagged side k go to side_streams[(k-1) % nside] behind an event on `stream` (fork whenever a
+// side's run of launches begins); `stream` waits for every used side stream at the end of the range unless MV3D_RUN_NO_JOIN.
 int mv3d_plan_run_range_multi(mv3d_plan* p, int begin, int end, void* stream, void* const* side_streams, int nside, int flags) {
     if (!p) return mv3d::fail(MV3D_E_INVAL, "mv3d_plan_run_range: null plan");
     if (mv3d::g_rec) return mv3d::fail(MV3D_E_INVAL, "mv3d_plan_run_range: cannot run while recording");
@@ -167,10 +163,8 @@ int mv3d_plan_run_range_multi(mv3d_plan* p, int begin, int end, void* stream, vo
                 (void)hipStreamWaitEvent(s, p->join[k], 0);
             }
     };
-    const int held = (flags & MV3D_RUN_HOLD_CLASS2) ? 2 : -1;      // the caller issues that class itself (mv3d_plan_run_side)
     if (!p->profile) {
         for (int i = begin; i < end; ++i) {
-            if (p->ops[i].side == held) continue;
             int rc = p->ops[i].fn(stream_of(i));
             if (rc != MV3D_OK) return rc;
         }
@@ -192,7 +186,6 @@ int mv3d_plan_run_range_multi(mv3d_plan* p, int begin, int end, void* stream, vo
         p->pass_open = true;
     }
     for (int i = begin; i < end; ++i) {
-        if (p->ops[i].side == held) continue;
         const bool sel = p->ops[i].selected;
         hipStream_t so = stream_of(i);
         if (sel) (void)hipEventRecord(p->pool[p->used + 2 * i], so);
@@ -202,25 +195,6 @@ int mv3d_plan_run_range_multi(mv3d_plan* p, int begin, int end, void* stream, vo
     }
     join();
     if (end == n) { p->used = need; p->pass_open = false; }
-    return MV3D_OK;
-}
-
-// The launches of side class `cls` that a run with MV3D_RUN_HOLD_CLASS2 left out, in recorded order on `stream` (the caller has
-// ordered it behind whatever they depend on).  Profiled plans: the events go into the slots of the pass that run just closed.
-int mv3d_plan_run_side(mv3d_plan* p, int cls, void* stream) {
-    if (!p) return mv3d::fail(MV3D_E_INVAL, "mv3d_plan_run_side: null plan");
-    if (mv3d::g_rec) return mv3d::fail(MV3D_E_INVAL, "mv3d_plan_run_side: cannot run while recording");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t n = p->ops.size();
-    const bool prof = p->profile && p->used >= 2 * n;
-    for (size_t i = 0; i < n; ++i) {
-        if (p->ops[i].side != cls) continue;
-        const bool sel = prof && p->ops[i].selected;
-        if (sel) (void)hipEventRecord(p->pool[p->used - 2 * n + 2 * i], s);
-        int rc = p->ops[i].fn(s);
-        if (sel) (void)hipEventRecord(p->pool[p->used - 2 * n + 2 * i + 1], s);
-        if (rc != MV3D_OK) return rc;
-    }
     return MV3D_OK;
 }
 

@@ -762,8 +762,8 @@ __global__ __launch_bounds__(512) void cwgrad_kernel(const CwParams p) {
 
 // planning: eligible geometry -> number of slabs (0 = not eligible); every caller (workspace sizing, launch) goes through here
 // CUs a filter-gradient launch spreads its partial-filter slabs over: MV3D_WG_CUS (128 = half the chip, because these launches
-// share it with the data-gradient chain), or what mv3d_set_wgrad_cus() asked for -- the train step raises it to the whole
-// chip for the last filter gradients of the reverse pass, which run when the data-gradient chain has ended.
+// share it with the data-gradient chain), or what mv3d_set_wgrad_cus() asked for (a process-wide diagnostics override; the
+// train step never sets it).
 static int g_wg_cus_override = 0;
 static int wgrad_cus(int kh = 5) {
     static int wg_cus = -1, wg_cus3 = -1;

@@ -232,21 +232,11 @@ class ConvNode(Node):
         n, h, w, c = img.shape
         return _lib.conv_geom(n, h, w, c, feat.shape[3], kh, kw, sh, sw, img.ld, feat.ld)
 
-    wg_cus = 0          # CUs of this layer's filter-gradient launch (0 = the library's default, mv3d_set_wgrad_cus)
-
     def workspace_bytes(self, g):
-        old = g.lib.set_wgrad_cus(self.wg_cus)
-        try:
-            return g.lib.conv_workspace_bytes(C.byref(self.geom()))
-        finally:
-            g.lib.set_wgrad_cus(old)
+        return g.lib.conv_workspace_bytes(C.byref(self.geom()))
 
     def wgrad_partial_bytes(self, g):
-        old = g.lib.set_wgrad_cus(self.wg_cus)
-        try:
-            return int(g.lib.conv_wgrad_workspace_bytes(C.byref(self.geom())))
-        finally:
-            g.lib.set_wgrad_cus(old)
+        return int(g.lib.conv_wgrad_workspace_bytes(C.byref(self.geom())))
 
     def forward(self, g):
         geom = self.geom()
@@ -261,23 +251,17 @@ class ConvNode(Node):
         _ensure_premasked(g, y)
         geom = self.geom()
         # filter / bias gradients are side work (only Adam reads them): own scratch, may run on the side stream
-        kh, kw = self.k[0], self.k[1]
-        us = 12.0 + 2.0 * geom.N * geom.Ho * geom.Wo * kh * kw * geom.C * geom.K / 120e6      # rough kernel time, microseconds
-        ws_side = g.begin_side(us + 10.0, us if x.requires_grad else 0.0)
+        ws_side = g.begin_side()
         ws_len = g.ws_bytes
         if g._finalizing:
             # mv3d_grad_finalize_*: the per-slab partial sums stay in THIS layer's region of the arena until the one batched
             # reduction (+ optimiser) at the end of the pass has read them
             ws_side, ws_len = g._part_arena.data_ptr() + self._part_off, self._part_bytes
-        old_cus = g.lib.set_wgrad_cus(self.wg_cus)
-        try:
-            if self.transposed:
-                g.lib.deconv2d_wgrad(C.byref(geom), x.ptr, y.grad_ptr, self.w.grad_ptr, ws_side, ws_len, g.stream)
-            else:
-                g.lib.conv2d_wgrad(C.byref(geom), x.ptr, y.grad_ptr, self.w.grad_ptr,
-                                   self.b.grad_ptr if self.b is not None else None, ws_side, ws_len, g.stream)
-        finally:
-            g.lib.set_wgrad_cus(old_cus)      # process-global override: never leave it set behind a failed call
+        if self.transposed:
+            g.lib.deconv2d_wgrad(C.byref(geom), x.ptr, y.grad_ptr, self.w.grad_ptr, ws_side, ws_len, g.stream)
+        else:
+            g.lib.conv2d_wgrad(C.byref(geom), x.ptr, y.grad_ptr, self.w.grad_ptr,
+                               self.b.grad_ptr if self.b is not None else None, ws_side, ws_len, g.stream)
         g.end_side()
         self.w.has_grad = True
         if self.b is not None:
@@ -328,24 +312,11 @@ class LinearNode(Node):
         # the fused kernel reads x and dy with 16-byte loads: a channel slice at an odd offset takes fc_wgrad + adam_step_dev
         if g._fusing and g.lib.fc_wgrad_adam_supported(B, fin, fout, x.ld, y.ld) and x.ptr % 16 == 0 and y.grad_ptr % 16 == 0:
             # Single-GPU step: the matrix gradient never goes to HBM -- ApplyAdam runs in the epilogue of the filter-gradient
-            # kernel (mv3d_fc_wgrad_adam).  It rewrites the matrix, so it is recorded BEHIND the layer's data gradient (the
-            # last reader of the old weights; the side stream forks after it); the bias gradient takes the ordinary path.
+            # kernel (mv3d_fc_wgrad_adam), recorded by record_fused_update() at the end of the reverse pass.
             if x.requires_grad:
                 epi = _epi(mask_of=x)
                 g.lib.fc_dgrad(B, fin, fout, y.grad_ptr, y.ld, self.m.ptr, x.grad_ptr, x.ld, C.byref(epi), g.ws_ptr, g.ws_bytes, g.stream)
                 _note_grad_written(x, x.act != ACT_NONE)
-            def emit(g=g, self=self, x=x, y=y, B=B, fin=fin, fout=fout):
-                g.begin_side(60.0, 0.0, cls=2)          # its own stream: 400 MB of HBM traffic must not hold up the conv filter gradients
-                off = 4 * self.m.offset
-                if g.optimizer == 'adam':
-                    g.lib.fc_wgrad_adam(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr, g.adam_m.data_ptr() + off,
-                                        g.adam_v.data_ptr() + off, self.b.grad_ptr, g.opt_state.data_ptr() + 32, g.stream)
-                else:                                   # Momentum (slot) or GD (none): mv3d_fc_wgrad_sgd
-                    g.lib.fc_wgrad_sgd(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr,
-                                       g.accum.data_ptr() + off if g.accum is not None else None, self.b.grad_ptr,
-                                       g.opt_state.data_ptr() + 32, g.stream)
-                g.end_side()
-            g._deferred.append([g.fcadam_delay, emit])
             g._fused_vars.append(self.m)
             g._fused_nodes.append(self)
             self.m.has_grad = self.b.has_grad = True
@@ -356,7 +327,7 @@ class LinearNode(Node):
         side_dgrad = (x.requires_grad and fin <= 128 and fout <= 128 and x.grad_consumers <= 1 and
                       any(isinstance(n, LinearNode) and n.y.storage is x.storage and n.y.ch_off == x.ch_off and n.x.C <= 128
                           for n in g.nodes))
-        ws_side = g.begin_side(25.0, 32.0 if x.requires_grad else 0.0)
+        ws_side = g.begin_side()
         if side_dgrad:
             epi = _epi(mask_of=x)       # both gradients read dy: one launch (mv3d_fc_wgrad_dgrad)
             g.lib.fc_wgrad_dgrad(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr, self.m.grad_ptr, self.b.grad_ptr,
@@ -372,6 +343,25 @@ class LinearNode(Node):
             g.lib.fc_dgrad(B, fin, fout, y.grad_ptr, y.ld, self.m.ptr, x.grad_ptr, x.ld, C.byref(epi),
                            g.ws_ptr, g.ws_bytes, g.stream)
             _note_grad_written(x, x.act != ACT_NONE)
+
+    def record_fused_update(self, g):
+        """The fused filter gradient + optimiser of a matrix whose backward() left it out.  Graph.compile records it at the
+        end of the reverse pass, behind the layer's data gradient (the last reader of the old weights).  It streams 400 MB:
+        next to the other fc layers' weight streams and the latency-bound 8x8 / 4x4 convolutions it only fights for HBM,
+        next to the MFMA-bound tail of the filter-gradient chain it is free (measured at B = 64: right behind the layer
+        26.56k, 6 nodes behind 26.65k, end of the pass 26.83k images/s)."""
+        x, y = self.x, self.y
+        B, fin, fout = x.shape[0], x.C, y.C
+        g.begin_side(cls=2)         # its own stream: it must not hold up the conv filter gradients
+        off = 4 * self.m.offset
+        if g.optimizer == 'adam':
+            g.lib.fc_wgrad_adam(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr, g.adam_m.data_ptr() + off,
+                                g.adam_v.data_ptr() + off, self.b.grad_ptr, g.opt_state.data_ptr() + 32, g.stream)
+        else:                       # Momentum (slot) or GD (none): mv3d_fc_wgrad_sgd
+            g.lib.fc_wgrad_sgd(B, fin, fout, x.ptr, x.ld, y.grad_ptr, y.ld, self.m.ptr,
+                               g.accum.data_ptr() + off if g.accum is not None else None, self.b.grad_ptr,
+                               g.opt_state.data_ptr() + 32, g.stream)
+        g.end_side()
 
 
 class ActNode(Node):
@@ -567,17 +557,8 @@ class Graph:
         self.ws = None
         self.ws_ptr, self.ws_bytes = None, 0
         self.n_side = max(0, min(4, int(os.environ.get('MV3D_SIDE_STREAMS', '2'))))      # 0: single-stream reverse pass; class 1 conv filter gradients, class 2 fused fc optimiser
-        # fused fc optimiser launches are recorded this many graph nodes after their layer's data gradient (0 = right behind it;
-        # default: at the end of the reverse pass).  They stream 400 MB each: next to the other fc layers' weight streams and the
-        # latency-bound 8x8 / 4x4 convolutions they only fight for HBM, next to the MFMA-bound tail of the filter-gradient chain
-        # they are free (measured at B = 64: 0 -> 26.56k, 6 -> 26.65k, end -> 26.83k images/s; unfused bucketed Adam 26.03k)
-        self.fcadam_delay = int(os.environ.get('MV3D_FCADAM_DELAY', '1000000'))
-        self._deferred = []
         self.ws_side = []
         self.side_streams = None
-        self._side_rr = 0
-        self._clk_main = self._clk_side = 0.0
-        self.balance_streams = os.environ.get('MV3D_BALANCE', '0') != '0'     # measured: level clocks do not pay (concurrent kernels share the CUs)
         self.adam_stream = None
         self.adam_timing = None         # list of (start, end) events per optimiser launch when a bench wants them
         self.overlap_adam = os.environ.get('MV3D_OVERLAP_ADAM', '1') != '0'
@@ -597,9 +578,7 @@ class Graph:
         self.pipeline_fc = os.environ.get('MV3D_PIPELINE_FCADAM', '1') != '0'
         # data parallel, sharded optimiser: all-gathers of buckets first read at forward launch >= pipeline_dp_min_idx are deferred
         self.pipeline_dp = os.environ.get('MV3D_PIPELINE_DP', '1') != '0'
-        self.dp_join = os.environ.get('MV3D_DP_JOIN', '0') != '0'      # 1: the main stream joins the side streams at every bucket boundary (round-1 behaviour)
         self.pipeline_dp_min_idx = 8
-        self.fc_after_wgrads = os.environ.get('MV3D_FC_AFTER_WGRADS', '0') != '0'      # hold the fused fc optimiser until the conv filter gradients are done
         self._fused_nodes = []
         self._fwd_wait_idx = 0
         self._fc_event = None
@@ -850,7 +829,6 @@ class Graph:
             suffix = len(order)         # variables[suffix:] are complete
             cut_hi = self.flat_size
             gate = 0
-            self._clk_main = self._clk_side = 0.0
             for n in reversed(self.nodes):
                 n.backward(self)
                 if isinstance(n, LinearNode):
@@ -912,10 +890,7 @@ class Graph:
         if self.fuse_fc_adam and self.lr is not None and any(isinstance(n, LinearNode) for n in self.nodes):
             for t, (gw, gm) in zip(self.tensors, flags_after_forward):
                 t.grad_written, t.grad_masked = gw, gm
-            self._clk_main = self._clk_side = 0.0
-            self._side_rr = 0
             plan = lib.plan_create()
-            on_gpu = torch.device(self.device).type == 'cuda'
             self._finalized_in_plan = False
             if self.fuse_finalize:
                 # every conv layer gets its own region for its per-slab partial filters (they live until the end of the pass)
@@ -930,7 +905,6 @@ class Graph:
                 self._fin_pending, self._fin_vars, self._fin_done, self._fin_tables = 0, [], set(), []
             lib.plan_begin(plan)
             self._fusing = True
-            self._deferred = []
             try:
                 for n in reversed(self.nodes):
                     n.backward(self)
@@ -942,14 +916,8 @@ class Graph:
                         if self._fin_pending >= self.finalize_chunk_bytes:
                             self._finalize_commit()
                             lib.grad_finalize_begin()
-                    for d in self._deferred:
-                        d[0] -= 1
-                    for d in [d for d in self._deferred if d[0] < 0]:
-                        d[1]()
-                        self._deferred.remove(d)
-                for d in self._deferred:
-                    d[1]()
-                self._deferred = []
+                for n in self._fused_nodes:         # the fused fc optimiser goes behind the whole reverse pass
+                    n.record_fused_update(self)
                 if self._finalizing and self._fused_vars:
                     # everything else the optimiser owns: gradients that are already final in the flat buffer (the angle MLP, conv
                     # layers whose filter gradient is a single slab); the fused fc matrices and their biases are updated on the
@@ -1006,7 +974,7 @@ class Graph:
         tb = int(lib.grad_finalize_table_bytes())
         table = torch.empty(max(tb, 16), dtype=torch.uint8, device=self.device) if on_gpu else None
         self._fin_tables.append(table)
-        self.begin_side(20.0, 0.0)
+        self.begin_side()
         try:
             tp = table.data_ptr() if on_gpu else None
             if self.optimizer == 'adam':
@@ -1101,17 +1069,11 @@ class Graph:
         self._settle()
         self.lib.plan_run(self.plan_fwd, st)
 
-    def begin_side(self, cost_side=0.0, cost_main=0.0, cls=1):
+    def begin_side(self, cls=1):
         """Tag the calls recorded until end_side() as side work of class `cls` (1: conv / fc filter gradients, 2: the fused fc
-        optimiser; a class maps to side stream (cls - 1) % n_side); returns the scratch pointer reserved for that class.
-        cost_side / cost_main: estimated microseconds of the side work and of the main-stream work recorded next (only
-        used by the optional list schedule MV3D_BALANCE)."""
-        fork = self._clk_main
-        if self.n_side == 0 or (self.balance_streams and self._clk_side > self._clk_main + cost_main):
-            self._clk_main += cost_side + cost_main
+        optimiser; a class maps to side stream (cls - 1) % n_side); returns the scratch pointer reserved for that class."""
+        if self.n_side == 0:
             return self.ws_ptr
-        self._clk_side = max(self._clk_side, fork) + cost_side
-        self._clk_main += cost_main
         k = (cls - 1) % self.n_side
         self.lib.plan_side(k + 1)
         return self.ws_side[k].data_ptr()
@@ -1125,9 +1087,7 @@ class Graph:
         if self.n_side == 0 or torch.device(self.device).type != 'cuda':
             return None, 0
         if self.side_streams is None:
-            # MV3D_SIDE_PRIORITY: comma-separated stream priorities of the side streams (0 = default, -1 = high); measured: no gain
-            prio = [int(x) for x in os.environ.get('MV3D_SIDE_PRIORITY', '').split(',') if x.strip()]
-            self.side_streams = [torch.cuda.Stream(device=self.device, priority=(prio[k] if k < len(prio) else 0)) for k in range(self.n_side)]
+            self.side_streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n_side)]
             self._side_arr = (C.c_void_p * self.n_side)(*[st.cuda_stream for st in self.side_streams])
         return self._side_arr, self.n_side
 
@@ -1195,15 +1155,8 @@ class Graph:
         sides, ns = self._side_ptrs()
         st = self._stream_ptr()
         pipelined = self.pipeline_fc and ns >= 2 and self._fwd_wait_idx is not None
-        self.lib.plan_run_range_multi(self.plan_bwd_fused, 0, self.n_launch_bwd_fused, st, sides, ns,
-                                      (1 if pipelined else 0) | (2 if pipelined and self.fc_after_wgrads else 0))
+        self.lib.plan_run_range_multi(self.plan_bwd_fused, 0, self.n_launch_bwd_fused, st, sides, ns, 1 if pipelined else 0)
         fc_state = self.opt_state.data_ptr() + 32
-        if pipelined and self.fc_after_wgrads:
-            # flags bit 2 made the plan hold the class-2 launches back: issue them now, behind the conv filter gradients
-            for k, q in enumerate(self.side_streams):
-                if k != 1 % ns:
-                    self.side_streams[1 % ns].wait_stream(q)
-            self.lib.plan_run_side(self.plan_bwd_fused, 2, self.side_streams[1 % ns].cuda_stream)
         if pipelined:
             main = torch.cuda.current_stream(self.device)
             for k, q in enumerate(self.side_streams):
@@ -1290,7 +1243,7 @@ class Graph:
             # the segment's filter-gradient launches stay on their side streams: only the COMMUNICATION stream waits for them (the
             # main stream goes straight on with the next layers' data gradients instead of idling behind an 80 us fc filter gradient
             # at every bucket boundary)
-            self.lib.plan_run_range_multi(self.plan_bwd, begin, end, main, sides, ns, 1 if (on_gpu and not self.dp_join) else 0)
+            self.lib.plan_run_range_multi(self.plan_bwd, begin, end, main, sides, ns, 1 if on_gpu else 0)
             begin = end
             if hi <= lo:
                 continue

@@ -168,6 +168,36 @@ def test_absent_optimizer_key_is_the_adam_plan(b64_models):
     assert direct == ['adam_step_dev', 'adam_advance', 'adam_advance']
 
 
+def test_fused_fc_optimiser_closes_the_reverse_pass(lib, monkeypatch):
+    """LinearNode.record_fused_update: the four fused fc launches go on side class 2 behind every class-1 launch of the fused
+    reverse pass (conv / fc filter gradients, chunked finalisations), and only the last grad_finalize follows them."""
+    monkeypatch.delenv('MV3D_SIDE_STREAMS', raising=False)          # the default: two side streams
+    marks, cur = [], [None]
+    begin, side = lib.plan_begin, lib.plan_side
+
+    def plan_begin(p):
+        cur[0] = p
+        return begin(p)
+
+    def plan_side(k):
+        marks.append((cur[0], lib.plan_size(cur[0]), k))
+        return side(k)
+
+    monkeypatch.setattr(lib, 'plan_begin', plan_begin)
+    monkeypatch.setattr(lib, 'plan_side', plan_side)
+    g = _appflow(dict(B64)).graph
+    labels = _labels(g.plan_bwd_fused)
+    cls = [0] * len(labels)                 # the side class each launch was recorded under
+    for p, i, k in marks:
+        if p == g.plan_bwd_fused:
+            cls[i:] = [k] * (len(labels) - i)
+    fc = [i for i, k in enumerate(cls) if k == 2]
+    assert [labels[i] for i in fc] == ['fc_wgrad_adam_b3'] * 4
+    assert labels[fc[-1] + 1:] == ['grad_finalize_adam']
+    side1 = [i for i, k in enumerate(cls[:fc[-1] + 1]) if k == 1]
+    assert side1 and max(side1) < fc[0]
+
+
 @pytest.mark.parametrize("kind", sorted(KINDS))
 def test_conf_selects_the_fused_plan_of_the_optimizer(b64_models, kind):
     g, adam = b64_models[kind].graph, b64_models['adam'].graph

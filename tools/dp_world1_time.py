@@ -26,4 +26,4 @@ t0 = time.perf_counter()
 for _ in range(40):
     step()
 torch.cuda.synchronize()
-print("%s: %.4f ms per step" % ('single-GPU step' if '--single' in sys.argv else 'data-parallel schedule, world 1 (MV3D_DP_JOIN=%s)' % os.environ.get('MV3D_DP_JOIN', '0'), (time.perf_counter() - t0) / 40 * 1e3))
+print("%s: %.4f ms per step" % ('single-GPU step' if '--single' in sys.argv else 'data-parallel schedule, world 1', (time.perf_counter() - t0) / 40 * 1e3))
