@@ -73,6 +73,7 @@ STATUS_FUNCS = {
     "mv3d_tfrecord_open": [C.c_char_p, _i, C.POINTER(_vp)],
     "mv3d_tfrecord_read": [_vp, _i, _i, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(C.c_int)],
     "mv3d_u8_to_unit_f32": [_i64, _vp, _vp, _vp],
+    "mv3d_u8_process_image": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "mv3d_fill": [_vp, _i64, _f, _vp],
     "mv3d_adam_step": [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _vp],
     "mv3d_adam_step_dev": [_i64, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64), _vp],

@@ -3,10 +3,16 @@ TensorFlow.
 
 Mirrors `build_tfrecord_input` of dyn_mult_view/multi_view_model/utils/read_tf_records.py:15-85 and
 read_tf_records_multobj.py:15-158: glob `conf['data_dir']/*`, split the file list at `floor(train_val_split * n)`
-(:31-35), read `tf.train.Example` records with bytes features (raw uint8 images, 128*128*C) and the float feature
-`displacement[2]` (:55-64), decode to float32 / 255 (:90-112 -- the crop / bicubic resize there are identities at
-128 x 128), batch.  Writer side of the format: collect_data/scripts/collect_data_node.py:126-133,
-multi_view_model/utils/render_multiobj.py:551-570.
+(:31-35), read `tf.train.Example` records with bytes features (raw uint8 images, Hr*Wr*C) and the float feature
+`displacement[2]` (:55-64), `process_image` (:88-112: central square crop, bicubic resize to the model's size, / 255), batch.
+Writer side of the format: collect_data/scripts/collect_data_node.py:126-133, multi_view_model/utils/render_multiobj.py:551-570.
+
+Record size and model size: conf['record_image_size'] (an int or (H, W); the reference's ORIGINAL_HEIGHT / ORIGINAL_WIDTH) is
+the size of the images in the shards.  Absent, or equal to the model's input size, crop and resize are identities and the
+reader is the plain uint8 -> float32 / 255 with an exact size match demanded of every record.  Different, every image
+feature goes through `process_image` below -- on the device one mv3d_u8_process_image launch per feature per batch
+(csrc/process_image.hip), with device='cpu' the numpy float32 code of this module; the two agree bitwise.  The resize is
+TensorFlow 1.3's ResizeBicubic restated from its kernel (input path); TensorFlow itself was never run against it.
 
 On-disk format (TFRecord): per record `uint64 length | uint32 masked_crc32c(length) | bytes data | uint32
 masked_crc32c(data)`, masked = ((crc >> 15 | crc << 17) + 0xa282ead8) mod 2^32.  `data` is a serialized `tf.train.Example`:
@@ -17,7 +23,8 @@ Differences to the reference, by design: the reference shuffles file names per e
 into a 100*B-deep queue, so its batch order is non-deterministic; here the order is the (seeded) shuffled file order with
 records in file order.  The input thread does not parse records in Python: csrc/tfrecord.hip (mv3d_tfrecord_read) checks the
 CRCs, walks the Example and copies the requested features into pinned batch buffers without the GIL; images travel as uint8
-and become float32 / 255 on the device (mv3d_u8_to_unit_f32) on the reader's stream, `prefetch` batches ahead of the step.
+and become float32 / 255 on the device (mv3d_u8_to_unit_f32, or mv3d_u8_process_image when the record size differs) on the
+reader's stream, `prefetch` batches ahead of the step.
 The functions below (crc32c, parse_example, serialize_example, TFRecordWriter, read_records, decode_record) are the readable
 restatement of the same format, used by the writer and the tests.
 """
@@ -213,9 +220,89 @@ def split_files(conf, training=True):
     return filenames[:index] if training else filenames[index:]
 
 
-def decode_record(data, spec):
-    """spec: {graph input name: (H, W, C) or (2,)} -> {name: float32 array}; images are raw uint8 / 255 (:105-111)."""
+# TF 1.3 ResizeBicubic's coefficient table (A = -0.75): tab[2i] at x = i / 1024, tab[2i + 1] at x + 1
+_BICUBIC_TAB = None
+
+
+def bicubic_table():
+    global _BICUBIC_TAB
+    if _BICUBIC_TAB is None:
+        f = np.float32
+        A = f(-0.75)
+        x = (np.arange(1025) / 1024.0).astype(np.float32)
+        tab = np.empty(2050, np.float32)
+        tab[0::2] = ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+        x = x + f(1)
+        tab[1::2] = ((A * x - f(5) * A) * x + f(8) * A) * x - f(4) * A
+        _BICUBIC_TAB = tab
+    return _BICUBIC_TAB
+
+
+def _axis_taps(S, out):
+    """source indices [out, 4] (clamped) and weights [out, 4] of one axis, S -> out, align_corners = False, all float32"""
+    tab = bicubic_table()
+    loc = (np.float32(S) / np.float32(out)) * np.arange(out, dtype=np.float32)
+    fl = np.floor(loc)
+    off = np.rint((loc - fl) * np.float32(1024)).astype(np.int64)                    # round half to even, as lrintf
+    idx = np.clip(fl.astype(np.int64)[:, None] + np.arange(-1, 3), 0, S - 1)
+    return idx, np.stack([tab[2 * off + 1], tab[2 * off], tab[2 * (1024 - off)], tab[2 * (1024 - off) + 1]], axis=1)
+
+
+def process_image(src, out_hw):
+    """read_tf_records.py:88-112 on the host: uint8 [..., Hs, Ws, C] -> central square crop (side min(Hs, Ws)) -> TF 1.3 bicubic
+    resize to out_hw -> / 255, float32 [..., Ho, Wo, C]; no clipping.  Horizontal pass first, then vertical, each
+    ((v0*w0 + v1*w1) + v2*w2) + v3*w3 in float32: the order of mv3d_u8_process_image, whose result this equals bitwise."""
+    src = np.asarray(src)
+    if src.dtype != np.uint8 or src.ndim < 3:
+        raise ValueError("process_image wants a uint8 array [..., H, W, C]")
+    Ho, Wo = out_hw
+    Hs, Ws, Cc = src.shape[-3:]
+    S = min(Hs, Ws)
+    y0, x0 = (Hs - S) // 2, (Ws - S) // 2
+    ix, wx = _axis_taps(S, Wo)
+    iy, wy = _axis_taps(S, Ho)
+    wx, wy = wx[:, :, None], wy[:, :, None, None]
+    lead = src.shape[:-3]
+    out = np.empty((int(np.prod(lead, dtype=np.int64)), Ho, Wo, Cc), np.float32)
+    for n, img in enumerate(src.reshape((-1, Hs, Ws, Cc))):                          # per image: bounds the temporaries
+        v = img[y0:y0 + S, x0:x0 + S].astype(np.float32)
+        g = v[:, ix]                                                                 # [S, Wo, 4, C]
+        h = ((g[:, :, 0] * wx[:, 0] + g[:, :, 1] * wx[:, 1]) + g[:, :, 2] * wx[:, 2]) + g[:, :, 3] * wx[:, 3]
+        g = h[iy]                                                                    # [Ho, 4, Wo, C]
+        o = ((g[:, 0] * wy[:, 0] + g[:, 1] * wy[:, 1]) + g[:, 2] * wy[:, 2]) + g[:, 3] * wy[:, 3]
+        out[n] = o / np.float32(255.0)
+    return out.reshape(lead + (Ho, Wo, Cc))
+
+
+def _record_hw(size):
+    """conf['record_image_size']: an int or (H, W) -> (H, W)"""
+    hw = (size, size) if isinstance(size, (int, np.integer)) else tuple(size) if isinstance(size, (tuple, list)) else ()
+    if len(hw) != 2 or any((not isinstance(v, (int, np.integer))) or v < 1 for v in hw):
+        raise ValueError("record_image_size must be a positive int or (H, W), got %r" % (size,))
+    return int(hw[0]), int(hw[1])
+
+
+def record_spec(spec, record_size):
+    """{name: shape the model wants} -> {name: shape the record holds}: image features take record_size (None: the model's)."""
+    if record_size is None:
+        return dict(spec)
+    hw = _record_hw(record_size)
+    out = {}
+    for name, shape in spec.items():
+        if len(shape) == 1 or tuple(shape[:2]) == hw:
+            out[name] = tuple(shape)
+        else:
+            if shape[0] != shape[1]:
+                raise ValueError('Unequal height and width unsupported')             # read_tf_records.py:100-101
+            out[name] = hw + (shape[2],)
+    return out
+
+
+def decode_record(data, spec, record_size=None):
+    """spec: {graph input name: (H, W, C) or (2,)} -> {name: float32 array}; images are raw uint8 / 255 (:105-111), or, with
+    record_size (an int or (H, W)) different from the spec's size, raw uint8 [record_size, C] through process_image."""
     ex = parse_example(data)
+    rspec = record_spec(spec, record_size)
     out = {}
     for name, shape in spec.items():
         v = ex.get(RECORD_NAME.get(name, name))
@@ -228,16 +315,21 @@ def decode_record(data, spec):
             out[name] = a
         else:
             raw = np.frombuffer(v[0], np.uint8)
-            if raw.size != int(np.prod(shape)):
-                raise ValueError("feature %r has %d bytes, expected %s" % (name, raw.size, 'x'.join(map(str, shape))))
-            out[name] = raw.reshape(shape).astype(np.float32) / np.float32(255.0)
+            rshape = rspec[name]
+            if raw.size != int(np.prod(rshape)):
+                raise ValueError("feature %r has %d bytes, expected %s" % (name, raw.size, 'x'.join(map(str, rshape))))
+            if rshape != tuple(shape):
+                out[name] = process_image(raw.reshape(rshape), shape[:2])
+            else:
+                out[name] = raw.reshape(shape).astype(np.float32) / np.float32(255.0)
     return out
 
 
 class TFRecordInput:
     """Batches for a model: `next()` returns {graph input name: tensor on the model's device}.
 
-    conf keys as in the reference: data_dir, train_val_split, batch_size, optional test_mode (no shuffle, all files)."""
+    conf keys as in the reference: data_dir, train_val_split, batch_size, optional test_mode (no shuffle, all files); and
+    record_image_size (an int or (H, W)): the size of the images in the shards when it is not the model's (module docstring)."""
 
     def __init__(self, conf, input_shapes, training=True, device='cpu', seed=0, prefetch=4, verify=True, rank=0, world=1):
         self.files = split_files(conf, training)
@@ -248,6 +340,7 @@ class TFRecordInput:
         if world > 1:                                    # data parallel: every rank reads its own subset of the shards
             self.files = self.files[rank::world] or self.files
         self.spec = {k: tuple(s[1:]) for k, s in input_shapes.items()}
+        self.rspec = record_spec(self.spec, conf.get('record_image_size'))          # what a record holds, per feature
         self.batch = next(iter(input_shapes.values()))[0]
         self.shuffle = 'test_mode' not in conf
         self.rng = np.random.default_rng(seed)
@@ -269,7 +362,8 @@ class TFRecordInput:
     def _produce(self):
         """Input thread: the native reader (csrc/tfrecord.hip: framing, crc32c, Example parsing; no GIL held) copies the
         records' features straight into pinned batch buffers -- images stay uint8 on the host and over PCIe -- which are
-        uploaded on the reader's stream and turned into float32 / 255 there (mv3d_u8_to_unit_f32)."""
+        uploaded on the reader's stream and turned into float32 / 255 there (mv3d_u8_to_unit_f32; crop + bicubic resize + / 255
+        in mv3d_u8_process_image for the features whose record size is not the model's)."""
         reader = None
         try:
             import torch
@@ -278,14 +372,15 @@ class TFRecordInput:
             stream = torch.cuda.Stream(device=self.device) if cuda else None
             names = list(self.spec)
             kinds = [1 if len(self.spec[k]) == 1 else 0 for k in names]
-            sizes = [int(np.prod(self.spec[k])) * (4 if kd else 1) for k, kd in zip(names, kinds)]
+            sizes = [int(np.prod(self.rspec[k])) * (4 if kd else 1) for k, kd in zip(names, kinds)]
+            resize = [self.rspec[k] != self.spec[k] for k in names]
             c_names = (C.c_char_p * len(names))(*[RECORD_NAME.get(k, k).encode() for k in names])
             c_kinds = (C.c_int * len(names))(*kinds)
             c_sizes = (C.c_size_t * len(names))(*sizes)
             nring = self.q.maxsize + 2                    # a staging set is reused only after its upload has completed
             ring = []
             for _ in range(nring):
-                bufs = [torch.empty((self.batch,) + self.spec[k], dtype=torch.float32 if kd else torch.uint8) for k, kd in zip(names, kinds)]
+                bufs = [torch.empty((self.batch,) + self.rspec[k], dtype=torch.float32 if kd else torch.uint8) for k, kd in zip(names, kinds)]
                 if cuda:
                     bufs = [b.pin_memory() for b in bufs]
                 ring.append((bufs, (C.c_void_p * len(names))(*[b.data_ptr() for b in bufs]), [None]))
@@ -314,9 +409,13 @@ class TFRecordInput:
                 out = {}
                 if cuda:
                     with torch.cuda.stream(stream):
-                        for k, kd, b in zip(names, kinds, bufs):
+                        for k, kd, rs, b in zip(names, kinds, resize, bufs):
                             d = b.to(self.device, non_blocking=True)
-                            if not kd:
+                            if rs:
+                                f = torch.empty((self.batch,) + self.spec[k], dtype=torch.float32, device=self.device)
+                                lib.u8_process_image(d.data_ptr(), *d.shape, f.data_ptr(), *self.spec[k][:2], stream.cuda_stream)
+                                d = f
+                            elif not kd:
                                 f = torch.empty(d.shape, dtype=torch.float32, device=self.device)
                                 lib.u8_to_unit_f32(d.numel(), d.data_ptr(), f.data_ptr(), stream.cuda_stream)
                                 d = f
@@ -326,8 +425,11 @@ class TFRecordInput:
                     done[0] = ev
                 else:
                     ev = None
-                    for k, kd, b in zip(names, kinds, bufs):
-                        out[k] = b.clone() if kd else b.to(torch.float32) / np.float32(255.0)
+                    for k, kd, rs, b in zip(names, kinds, resize, bufs):
+                        if rs:
+                            out[k] = torch.from_numpy(process_image(b.numpy(), self.spec[k][:2]))
+                        else:
+                            out[k] = b.clone() if kd else b.to(torch.float32) / np.float32(255.0)
                 self.q.put((out, ev))
         except BaseException as e:       # surfaced by next()
             self._err = e

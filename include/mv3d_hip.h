@@ -85,6 +85,17 @@ int mv3d_tfrecord_read(mv3d_tfrecord_reader* r, int max_records, int first, int 
 void mv3d_tfrecord_close(mv3d_tfrecord_reader* r);
 int mv3d_u8_to_unit_f32(int64_t count, const void* src, void* dst, void* stream);
 
+/* The reference's process_image (read_tf_records.py:88-112) for records whose size differs from the model's input, one launch:
+ * src uint8 [n, hs, ws, c] -> central square crop of side S = min(hs, ws) (rows / columns from (side - S) / 2) -> TensorFlow 1.3
+ * ResizeBicubic, align_corners = False, S x S -> ho x wo -> / 255 -> dst float32 [n, ho, wo, c]; no clipping.  Per axis, all in
+ * fp32 without contraction: scale = (float)S / (float)out, loc = scale * (float)o, fl = floor(loc), off = lrintf((loc - fl) * 1024),
+ * taps fl-1 .. fl+2 clamped to [0, S-1], weights from TF's coefficient table (A = -0.75) at off and 1024 - off; horizontal pass
+ * first, then vertical, each ((v0*w0 + v1*w1) + v2*w2) + v3*w3 (input path).  S == out reproduces
+ * mv3d_u8_to_unit_f32 bitwise.
+ * MV3D_E_INVAL before any launch: a null pointer; n, hs, ws, ho, wo < 1; c outside 1 .. 4; a side above 4096; dst not 16-byte
+ * aligned; n*hs*ws*c or n*ho*wo*c >= 2^31 - 2^21 (32-bit indices).  Allocates nothing, keeps no state. */
+int mv3d_u8_process_image(const void* src, int n, int hs, int ws, int c, void* dst, int ho, int wo, void* stream);
+
 /* CRC-32C of a host buffer: the record checksum of the reference's TFRecord shards (multi_view_model/utils/read_tf_records.py:46-48
  * reads them through tf.TFRecordReader); used by dynamic_multiview_3d_amd/read_tf_records.py */
 uint32_t mv3d_crc32c(const void* data, size_t n);
