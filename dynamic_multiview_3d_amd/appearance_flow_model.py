@@ -44,6 +44,10 @@ class AppearanceFlowModel(ModelBase):
         self.loss = euclidean_loss(self.gen, self.image1)
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
+    def eval_pairs(self):
+        """The generated view against image1; the reader's images are uint8 / 255 (utils/read_tf_records.py:111): max_val 1."""
+        return [('image', self.gen, self.image1, 1.0)]
+
     def buildModel(self):
         image0 = self.image0
 

@@ -111,6 +111,16 @@ class Base_Prediction_Model(ModelBase):
             self.loss += euclidean_loss(self.gen_dimage1, self.dimage1) * self.conf['depth_lr_factor']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
+    def eval_pairs(self):
+        """Colour and / or depth prediction against its target, according to use_color / use_depth; the reader's images and
+        depth images are uint8 / 255 (utils/read_tf_records.py:111): max_val 1."""
+        pairs = []
+        if 'use_color' in self.conf:
+            pairs.append(('image', self.gen_image1, self.image1, 1.0))
+        if 'use_depth' in self.conf:
+            pairs.append(('depth', self.gen_dimage1, self.dimage1, 1.0))
+        return pairs
+
     def visualize(self, sess=None, **feeds):
         """One forward pass, then the reference's qualitative outputs (visualize.py)."""
         from . import visualize as _v

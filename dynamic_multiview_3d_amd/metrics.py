@@ -1,0 +1,159 @@
+"""Per-image quality metrics of a prediction against its target: L1, MSE / PSNR and SSIM.
+
+`image_metrics` is the host mirror of mv3d_image_metrics (include/mv3d_hip.h, csrc/metrics.hip): it runs on device memory and
+returns a device tensor, so a test split can be scored without copying a prediction to the host.  `image_metrics_host` is the
+numpy restatement of the same definition; `ModelBase.evaluate` uses it on a machine without a GPU.
+
+Definition (per image n of [N,H,W,C] operands a, b):
+  l1   = mean over the H*W pixels of sum_c |a-b|            -- the per-image form of l1_loss, mv3d/utils/tf_utils.py:22-23
+  mse  = mean over the H*W*C elements of (a-b)^2;  psnr = 10 log10(max_val^2 / mse), inf when mse == 0
+  ssim = Wang et al. 2004 in the form tf.image.ssim computes it.  F is the 11-tap Gaussian (sigma 1.5, normalised to sum 1)
+         applied separably over fully-inside windows, so the map is (H-10) x (W-10) per channel; c1 = (0.01 max_val)^2,
+         c2 = (0.03 max_val)^2, mx = F(a), my = F(b),
+           lum = (2 mx my + c1) / (mx^2 + my^2 + c1)
+           cs  = (2 F(a b) - 2 mx my + c2) / (F(a a + b b) - (mx^2 + my^2) + c2)
+         ssim = mean of lum * cs over the windows and the channels.
+"""
+import math
+
+import numpy as np
+
+WINDOW_TAPS = 11
+WINDOW_SIGMA = 1.5
+K1, K2 = 0.01, 0.03
+L1, MSE, SSIM = 0, 1, 2         # columns of the [N,3] result
+
+
+def ssim_window(dtype=np.float64):
+    """The 11 normalised Gaussian weights.  Computed in double with the C library's exp and an in-order sum -- the same steps as
+    mv3d_image_metrics takes -- then rounded to `dtype` once."""
+    g = [math.exp(-float((k - WINDOW_TAPS // 2) ** 2) / (2.0 * WINDOW_SIGMA * WINDOW_SIGMA)) for k in range(WINDOW_TAPS)]
+    s = 0.0
+    for v in g:
+        s += v
+    return np.array([v / s for v in g], np.float64).astype(dtype)
+
+
+def _valid_filter(x, w):
+    """F over [N,H,W,C]: horizontal pass, then vertical pass, taps added in index order (the kernel's order)."""
+    taps = len(w)
+    wo, ho = x.shape[2] - taps + 1, x.shape[1] - taps + 1
+    h = w[0] * x[:, :, 0:wo]
+    for k in range(1, taps):
+        h = h + w[k] * x[:, :, k:k + wo]
+    v = w[0] * h[:, 0:ho]
+    for k in range(1, taps):
+        v = v + w[k] * h[:, k:k + ho]
+    return v
+
+
+def ssim_map(a, b, max_val, dtype=np.float64):
+    """lum * cs at every fully-inside window: [N, H-10, W-10, C] in `dtype` arithmetic."""
+    dtype = np.dtype(dtype).type
+    a, b = np.asarray(a).astype(dtype), np.asarray(b).astype(dtype)
+    if a.shape != b.shape or a.ndim != 4:
+        raise ValueError("ssim: operands must be [N,H,W,C] of one shape, got %s and %s" % (a.shape, b.shape))
+    if a.shape[1] < WINDOW_TAPS or a.shape[2] < WINDOW_TAPS:
+        raise ValueError("ssim: images of %d x %d are smaller than the %d-tap window" % (a.shape[1], a.shape[2], WINDOW_TAPS))
+    max_val = float(np.float32(max_val))                     # the C ABI takes a float
+    if not math.isfinite(max_val) or max_val <= 0:
+        raise ValueError("ssim: max_val must be finite and positive")
+    k1, k2 = K1 * max_val, K2 * max_val
+    c1, c2 = dtype(k1 * k1), dtype(k2 * k2)
+    w = ssim_window(dtype)
+    two = dtype(2)
+    mx, my = _valid_filter(a, w), _valid_filter(b, w)
+    sab = _valid_filter(a * b, w)
+    s2 = _valid_filter(a * a + b * b, w)
+    num0 = (mx * my) * two
+    den0 = mx * mx + my * my
+    lum = (num0 + c1) / (den0 + c1)
+    cs = ((sab * two - num0) + c2) / ((s2 - den0) + c2)
+    return lum * cs
+
+
+def image_metrics_host(pred, target, max_val=1.0, dtype=np.float64):
+    """[N,3] = (l1, mse, ssim) per image, every step in `dtype` arithmetic (see the module docstring)."""
+    dt = np.dtype(dtype).type
+    m = ssim_map(pred, target, max_val, dt)
+    a, b = np.asarray(pred).astype(dt), np.asarray(target).astype(dt)
+    d = a - b
+    out = np.empty((a.shape[0], 3), dt)
+    out[:, L1] = np.abs(d).sum(axis=3, dtype=dt).mean(axis=(1, 2), dtype=dt)
+    out[:, MSE] = (d * d).mean(axis=(1, 2, 3), dtype=dt)
+    out[:, SSIM] = m.mean(axis=(1, 2, 3), dtype=dt)
+    return out
+
+
+def psnr(mse, max_val=1.0):
+    """10 log10(max_val^2 / mse), elementwise in float64; inf where mse == 0."""
+    mse = np.asarray(mse, np.float64)
+    with np.errstate(divide='ignore'):
+        return 10.0 * np.log10(float(max_val) ** 2 / mse)
+
+
+# ---------------------------------------------------------------------------------------------- device side
+def channel_view(t, offset, channels):
+    """Channels [offset, offset + channels) of a graph Tensor as a view (what tf.split / tf.slice give); usable after the graph
+    is compiled, adds no node."""
+    from .graph import Tensor
+    if offset < 0 or channels < 1 or offset + channels > t.C:
+        raise ValueError("channels [%d, %d) of a %d-channel tensor" % (offset, offset + channels, t.C))
+    return Tensor(t.graph, t.shape[:-1] + (channels,), storage=t.storage, ch_off=t.ch_off + offset, act=t.act, leak=t.leak)
+
+
+def _operand(x, what):
+    """(data pointer, shape, pixel stride, torch device or None) of a graph Tensor or a torch device tensor."""
+    import torch
+    if torch.is_tensor(x):
+        if x.dim() != 4 or x.dtype != torch.float32:
+            raise ValueError("image_metrics: %s must be float32 [N,H,W,C], got %s %s" % (what, x.dtype, tuple(x.shape)))
+        n, h, w, c = x.shape
+        ld = x.stride(2)
+        if x.stride(3) != 1 or x.stride(1) != w * ld or x.stride(0) != h * w * ld or ld < c:
+            raise ValueError("image_metrics: %s must be NHWC with one pixel stride (a channel slice of a dense tensor), "
+                             "strides %s" % (what, x.stride()))
+        return x.data_ptr(), (n, h, w, c), ld, x.device
+    if len(x.shape) != 4:
+        raise ValueError("image_metrics: %s must be [N,H,W,C], got %s" % (what, x.shape))
+    return x.ptr, tuple(x.shape), x.ld, x.graph.device
+
+
+_workspaces = {}        # torch device -> uint8 workspace tensor, grown on demand (calls on one stream share it in order)
+
+
+def _workspace(device, nbytes):
+    import torch
+    ws = _workspaces.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 4096), dtype=torch.uint8, device=device)
+        _workspaces[device] = ws
+    return ws
+
+
+def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
+    """mv3d_image_metrics on device memory.  pred / target: graph Tensors (channel views from split included) or torch device
+    tensors, [N,H,W,C] float32.  out: an optional dense float32 [N,3] device tensor to write into.  Asynchronous on `stream`
+    (a raw stream handle; default: torch's current stream of the operands' device).  Returns the [N,3] device tensor with
+    columns (l1, mse, ssim)."""
+    import torch
+    from . import _lib
+    pa, shape, a_ld, dev = _operand(pred, 'pred')
+    pb, shape_b, b_ld, dev_b = _operand(target, 'target')
+    if shape != shape_b:
+        raise ValueError("image_metrics: pred %s and target %s differ in shape" % (shape, shape_b))
+    dev = torch.device(dev)
+    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
+        raise _lib.Mv3dError("image_metrics runs on the GPU (operands are on %s); image_metrics_host is the numpy form" % dev)
+    n, h, w, c = shape
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (n, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("image_metrics: out must be a dense float32 [%d,3] tensor" % n)
+    lib = _lib.lib()
+    nbytes = int(lib.image_metrics_workspace_bytes(n, h, w, c))
+    ws = _workspace(out.device, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+    lib.image_metrics(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), out.data_ptr(), ws.data_ptr(), nbytes, stream)
+    return out

@@ -135,6 +135,65 @@ class ModelBase(object):
         self.graph.run_forward()
         return self.graph.loss_buf[0]
 
+    # ---- quantitative evaluation
+    def eval_pairs(self):
+        """[(name, prediction tensor, target tensor, max_val)]: what evaluate() scores.  max_val is the dynamic range of the
+        TARGET as the reader / the reference's loader produces it; each model class states where its value comes from."""
+        raise NotImplementedError("%s defines no eval_pairs()" % type(self).__name__)
+
+    def evaluate(self, data, num_batches=19):
+        """The quantitative counterpart of mv3d.test() (mv3d/nobg_dm.py:117-149): forward(**data.next()) num_batches times
+        (19 = the reference's test_iter), the loss averaged over the batches (:143-145), and per-image L1 / PSNR / SSIM of every
+        eval_pairs() entry averaged over the images (metrics.py; PSNR is averaged per image, an image with mse == 0 makes it inf).
+
+        On the GPU every batch appends its [N,3] metrics (mv3d_image_metrics) and its loss to device buffers and the host
+        synchronises once, after the last batch.  On a CPU graph the numpy form (image_metrics_host) scores each batch.
+        Only forward passes run: parameters, optimiser slots and the step counter are left as they were.
+        Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
+        from . import metrics
+        g = self.graph
+        num_batches = int(num_batches)
+        if num_batches < 1:
+            raise ValueError("evaluate: num_batches must be at least 1")
+        pairs = self.eval_pairs()
+        if not pairs:
+            raise RuntimeError("evaluate: the built graph has no prediction / target pair")
+        n = pairs[0][1].shape[0]
+        have_loss = g.loss_expr is not None
+        on_gpu = g.device.type == 'cuda'
+        if on_gpu:
+            scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
+            losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
+        else:
+            scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
+            losses = np.zeros(num_batches, np.float64)
+        for i in range(num_batches):
+            loss = self.forward(**data.next())
+            if on_gpu:
+                for j, (_, pred, target, max_val) in enumerate(pairs):
+                    metrics.image_metrics(pred, target, max_val, out=scores[i, j])
+                if have_loss:
+                    losses[i].copy_(loss, non_blocking=True)
+            else:
+                for j, (_, pred, target, max_val) in enumerate(pairs):
+                    scores[i, j] = metrics.image_metrics_host(pred.numpy(), target.numpy(), max_val)
+                if have_loss:
+                    losses[i] = float(loss)
+        if on_gpu:
+            packed = torch.cat([scores.reshape(-1), losses]).cpu()          # the one synchronisation
+            scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
+            losses = packed[scores.size:].numpy().astype(np.float64)
+        result = {}
+        if have_loss:
+            result['loss'] = float(losses.mean())
+        for j, (name, _, _, max_val) in enumerate(pairs):
+            s = scores[:, j].reshape(-1, 3)
+            result[name + '/l1'] = float(s[:, metrics.L1].mean())
+            result[name + '/psnr'] = float(metrics.psnr(s[:, metrics.MSE], max_val).mean())
+            result[name + '/ssim'] = float(s[:, metrics.SSIM].mean())
+        result['images'] = num_batches * n
+        return result
+
     # ---- data-parallel hook
     def enable_data_parallel(self, world_size, group=None, comm=None, mode=None):
         """comm: parallel.RcclComm (the product path: RCCL through the C ABI) or parallel.TorchComm (default: torch.distributed

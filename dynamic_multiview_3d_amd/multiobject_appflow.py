@@ -195,6 +195,13 @@ class MultiObjectAppFlow(ModelBase):
 
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
+    def eval_pairs(self):
+        """Every gen_* output the conf built against the reader tensor its loss term compares it with (unmasked: the per-object
+        masks of masked_image_loss are not applied).  All reader images are uint8 / 255 (utils/read_tf_records.py:111): max_val 1."""
+        names = ('image1', 'image1_only0', 'image1_only1', 'depth1', 'depth1_only0', 'depth1_only1', 'image1_mask0', 'image1_mask1')
+        return [(name, getattr(self, 'gen_' + name), getattr(self, name), 1.0)
+                for name in names if getattr(self, 'gen_' + name) is not None]
+
     def visualize(self, sess=None, **feeds):
         """One forward pass, then the reference's qualitative outputs (visualize.py)."""
         from . import visualize as _v

@@ -85,6 +85,18 @@ class _MV3DBase(ModelBase):
     def build_loss(self):
         raise NotImplementedError
 
+    fourth_channel = None       # (pair name, max_val) of the 4-channel variants
+
+    def eval_pairs(self):
+        """The colour channels of gen against those of images2: the loader maps colour to (x / 255 - 0.5) * 1.5
+        (mv3d/utils/tf_utils.py:179), a range of 1.5.  The fourth channel of the 4-channel variants is its own pair."""
+        from .metrics import channel_view
+        if self.gen.C == 3:
+            return [('image', self.gen, self.images2, 1.5)]
+        name, max_val = self.fourth_channel
+        return [('image', channel_view(self.gen, 0, 3), channel_view(self.images2, 0, 3), 1.5),
+                (name, channel_view(self.gen, 3, 1), channel_view(self.images2, 3, 1), max_val)]
+
     def _minimize(self):
         self.train_op = optimizer_from_conf(self.conf, self.learning_rate, beta1=0.9).minimize(self.loss, self.graph)
 
@@ -100,6 +112,7 @@ class mv3d_nobg_nodm(_MV3DBase):
 class mv3d_nobg_dm(_MV3DBase):
     """mv3d/nobg_dm.py: RGB in, RGB + depth map out; loss = L2(colour) + 0.1 * L1(depth) (:85-92)."""
     output_shape = [128, 128, 4]
+    fourth_channel = ('depth', 1.5)         # depth maps load as (x / 65535 - 0.5) * 1.5 (mv3d/utils/tf_utils.py:192)
 
     def build_loss(self):
         gt_cm, gt_dm = split(self.images2, [3, 1], axis=3)
@@ -113,6 +126,7 @@ class mv3d_bg_nodm(_MV3DBase):
     0.1 * L2(0.75 * silhouette, predicted silhouette) (:85-93)."""
     output_shape = [128, 128, 4]
     bg = True
+    fourth_channel = ('mask', 1.0)          # the target silhouette itself, in [0, 1] (the loss compares against 0.75 x it, bg_nodm.py:88)
 
     def build_loss(self):
         gt_cm, gt_sm = split(self.images2, [3, 1], axis=3)

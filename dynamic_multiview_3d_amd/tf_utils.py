@@ -370,3 +370,4 @@ def load_snapshot(saver, session, path):
 
 
 from .visualize import save_images, rescale_image, rescale_dm      # noqa: E402,F401  (tf_utils.py:101-147)
+from .summary import log_value                                     # noqa: E402,F401  (tf_utils.py:11-15)

@@ -11,7 +11,13 @@ Input: the TFRecord shards under conf['data_dir'] (read_tf_records.py); when tha
 --synthetic, seeded synthetic batches shaped like the reader's tensors.
 
 --visualize <checkpoint name> restores output_dir/<name> and writes the model's qualitative outputs (visualize.py).
-Not ported: TF summaries (a JSON-lines log is written instead).
+--evaluate <checkpoint name> [--eval_batches N] restores output_dir/<name>, scores N batches (default 19, the reference's
+test_iter, mv3d/nobg_dm.py:118) of the `test` split -- or of synthetic batches with --synthetic -- with model.evaluate()
+(loss, per-image L1 / PSNR / SSIM), prints the result and writes it to output_dir/eval_<name>.json.
+--event_log additionally writes TensorFlow event files (summary.py, the counterpart of mv3d/utils/tf_utils.py:11-15) under
+conf['event_log_dir'] (default output_dir): `training_loss` and `val_loss` where the JSON-lines log gets them, and with
+--evaluate `test_loss` and the metrics at the checkpoint's iteration.  Without the flag only the JSON-lines log is written.
+Not ported: image and histogram summaries.
 """
 import argparse
 import importlib
@@ -24,6 +30,8 @@ import types
 
 import numpy as np
 import torch
+
+from .summary import log_value
 
 SUMMARY_INTERVAL = 400      # train.py:24
 VAL_INTERVAL = 500          # train.py:27
@@ -68,6 +76,9 @@ class SyntheticData:
                 if len(t.shape) == 2:
                     if name == 'displacement':
                         a = rng.normal(10, 10, t.shape) * rng.choice([-1, 1], t.shape)
+                    elif name == 'labels':          # mv3d: [radius, sin / cos elevation, sin / cos azimuth] (mv3d/utils/tf_utils.py:184-190)
+                        rad, el, az = rng.uniform(0.5, 1.5, t.shape[0]), rng.uniform(0, 0.7, t.shape[0]), rng.uniform(-3.14, 3.14, t.shape[0])
+                        a = np.stack([rad, np.sin(el), np.cos(el), np.sin(az), np.cos(az)], 1)
                     else:
                         a = np.stack([rng.uniform(-1, 1, t.shape[0]), rng.uniform(-6.28, 6.28, t.shape[0])], 1)
                 else:
@@ -96,6 +107,38 @@ class SyntheticData:
         return b
 
 
+def _event_writer(conf):
+    from .summary import FileWriter
+    return FileWriter(conf.get('event_log_dir') or conf['output_dir'])
+
+
+def evaluate_checkpoint(model, conf, name, data, num_batches, event_log=False, write=True):
+    """--evaluate: restore output_dir/<name>, model.evaluate() over num_batches batches of `data`, print the result and write
+    output_dir/eval_<name>.json; with event_log also `test_loss` (mv3d/nobg_dm.py:148-149) and every metric as scalars at the
+    iteration the checkpoint's name ends in (0 when it ends in none, like the final `model`)."""
+    import re
+    path = conf['output_dir'] + '/' + name
+    model.saver.restore(None, path)
+    print('restore done.')
+    result = model.evaluate(data, num_batches)
+    m = re.match('.*?([0-9]+)$', name)
+    result['iteration'] = int(m.group(1)) if m else 0
+    result['checkpoint'] = name
+    print(json.dumps(result))
+    if write:
+        with open(os.path.join(conf['output_dir'], 'eval_%s.json' % name), 'w') as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write('\n')
+        if event_log:
+            events = _event_writer(conf)
+            for key, value in result.items():
+                if key in ('images', 'iteration', 'checkpoint'):
+                    continue
+                log_value(events, value, 'test_loss' if key == 'loss' else key, result['iteration'])
+            events.close()
+    return result
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--hyper', default='../../tensorflowdata/appflow_offset/conf.py', help='hyperparameters configuration file')
@@ -104,7 +147,12 @@ def main(argv=None):
     ap.add_argument('--pretrained', default=None, help='path to model file from which to resume training')
     ap.add_argument('--num_iterations', type=int, default=None, help='override conf["num_iterations"]')
     ap.add_argument('--synthetic', action='store_true', help='ignore conf["data_dir"] and train on synthetic batches')
+    ap.add_argument('--evaluate', default='', help='model within hyperparameter folder to score on the test split (loss, L1, PSNR, SSIM)')
+    ap.add_argument('--eval_batches', type=int, default=19, help='batches --evaluate scores (the reference tests 19)')
+    ap.add_argument('--event_log', action='store_true', help='also write the scalars as TensorFlow event files')
     FLAGS = ap.parse_args(argv)
+    if FLAGS.visualize and FLAGS.evaluate:
+        ap.error('--visualize and --evaluate exclude each other')
 
     conf = load_conf(FLAGS.hyper)
     if FLAGS.visualize:                                               # train.py:47-55
@@ -113,6 +161,9 @@ def main(argv=None):
         conf['visualize'] = conf['output_dir'] + '/' + FLAGS.visualize
         conf['event_log_dir'] = '/tmp'
         conf['batch_size'] = 10
+        conf['test_mode'] = ''
+    if FLAGS.evaluate:                                                # the test split, as --visualize selects it
+        conf['data_dir'] = '/'.join(str.split(conf.get('data_dir') or '', '/')[:-1] + ['test'])
         conf['test_mode'] = ''
     if FLAGS.num_iterations is not None:
         conf['num_iterations'] = FLAGS.num_iterations
@@ -153,6 +204,10 @@ def main(argv=None):
         model.visualize(None, **train_data.next())
         return model
 
+    if FLAGS.evaluate:
+        return evaluate_checkpoint(model, conf, FLAGS.evaluate, train_data, FLAGS.eval_batches, FLAGS.event_log and rank == 0,
+                                   write=rank == 0)
+
     itr_0 = 0
     if FLAGS.pretrained is not None:
         conf['pretrained_model'] = FLAGS.pretrained
@@ -169,6 +224,7 @@ def main(argv=None):
         print('-------------------------------------------------------------------')
         os.makedirs(conf['output_dir'], exist_ok=True)
         log = open(os.path.join(conf['output_dir'], 'train_log.jsonl'), 'a')
+    events = _event_writer(conf) if FLAGS.event_log and rank == 0 else None
 
     # The launch thread runs tens of milliseconds ahead of the GPU; a full cyclic-GC pass over everything the imports and
     # the graph construction left behind takes longer than that and drains the queues.  Move those objects to the
@@ -187,10 +243,14 @@ def main(argv=None):
             if rank == 0:
                 print(str(itr) + ' ' + str(c))
                 log.write(json.dumps({'itr': itr, 'training_loss': c}) + '\n')
+                if events is not None:
+                    log_value(events, c, 'training_loss', itr)
         if itr % VAL_INTERVAL == 0 and itr != 0:
             vc = float(model.forward(**val_data.next()))
             if rank == 0:
                 log.write(json.dumps({'itr': itr, 'val_loss': vc}) + '\n')
+                if events is not None:
+                    log_value(events, vc, 'val_loss', itr)
         if itr % SAVE_INTERVAL == 0 and itr != 0:
             model.graph.gather_optimizer_state()        # collective: the sharded optimiser's slots, complete on every rank
             if rank == 0:
@@ -203,11 +263,15 @@ def main(argv=None):
             print('time per iteration: {0}'.format(avg_t_iter))
             print('expected for complete training: {0}h '.format(avg_t_iter / 3600 * conf['num_iterations']))
             log.flush()
+            if events is not None:
+                events.flush()
     model.graph.gather_optimizer_state()
     if rank == 0:
         print('Saving model.')
         saver.save(None, conf['output_dir'] + '/model')
         log.close()
+        if events is not None:
+            events.close()
         print('Training complete')
     return model
 

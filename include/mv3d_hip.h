@@ -254,6 +254,29 @@ int mv3d_fill(void* dst, int64_t count, float value, void* stream);
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
 
+/* ---- image metrics: per-image L1, MSE and SSIM of a prediction against its target ---------------------------------
+ * a, b [N,H,W,C] fp32 with pixel strides a_ld / b_ld (channel-slice views work), C in 1..4.  out [N,3] dense fp32:
+ *   out[n][0] = mean over the H*W pixels of sum_c |a-b|     (the per-image form of l1_loss, tf_utils.py:22-23)
+ *   out[n][1] = mean over the H*W*C elements of (a-b)^2     (PSNR = 10 log10(max_val^2 / out[n][1]) on the host)
+ *   out[n][2] = SSIM (Wang et al. 2004) as tf.image.ssim computes it: F = the 11-tap Gaussian window (sigma 1.5, normalised to
+ *               sum 1) applied separably over fully-inside windows only, so the map is (H-10) x (W-10) per channel;
+ *               c1 = (0.01 max_val)^2, c2 = (0.03 max_val)^2, mx = F(a), my = F(b),
+ *               lum = (2 mx my + c1) / (mx^2 + my^2 + c1),
+ *               cs  = (2 F(a b) - 2 mx my + c2) / (F(a a + b b) - (mx^2 + my^2) + c2),
+ *               value = mean of lum * cs over the windows and the C channels.
+ * The window pass and the SSIM expression are fp32 without contraction (horizontal pass first, taps added in index order: the
+ * map is the one metrics.py image_metrics_host computes in float32); the differences of L1 / MSE and every sum are in double.
+ * a == b gives exactly {0, 0, 1}.  Sums run in a fixed order without atomics: the same inputs give the same bits, run after run.
+ * The call allocates nothing and keeps no state outside `workspace` (16-byte aligned, mv3d_image_metrics_workspace_bytes()
+ * bytes, which is 0 for a shape the entry refuses): the per-tile sums live there between its two launches.
+ * MV3D_E_INVAL before any launch: N < 1; H or W < 11; C outside 1..4; H or W > 32768, or N * ceil(H/32) * ceil(W/32) >= 2^31
+ * (the tile index is a 32-bit grid index; pixel offsets are 64-bit); a_ld or b_ld < C; max_val not finite or <= 0; a null
+ * pointer; a, b or out not 4-byte aligned.  MV3D_E_WORKSPACE: workspace too small or not 16-byte aligned.  On any error out is
+ * left untouched. */
+size_t mv3d_image_metrics_workspace_bytes(int N, int H, int W, int C);
+int mv3d_image_metrics(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, void* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
  *   p -= m*alpha/(sqrt(v)+eps).   One fused pass over a flat fp32 buffer; grad_scale multiplies g
