@@ -23,6 +23,8 @@ struct OpInfo {
 const char* intern_label(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
 bool recording();
+// mv3d_loss_overwrite_next(): true once for the calling thread's next loss entry point, which then stores its term (elem.hip)
+bool take_loss_overwrite();
 void record(std::function<int(hipStream_t)> fn, const OpInfo& info);
 
 // Optimiser fused into a gradient kernel's epilogue (fc_wgrad_b3_kernel, grad_finalize_kernel): none (store the gradient),

@@ -23,10 +23,15 @@ __device__ unsigned g_loss_ticket[LOSS_ROWS];
 // mv3d_loss_overwrite_next(): the next loss call of this thread STORES its sum instead of adding it to the accumulator -- the
 // first loss term of a recorded step, which then needs no launch that clears the accumulator (flag = bit 8 of the row).
 static thread_local bool g_loss_overwrite = false;
+// reads and clears the flag: the one way a loss entry point (here or in ssim_loss.hip) learns of it
+bool take_loss_overwrite() {
+    const bool v = g_loss_overwrite;
+    g_loss_overwrite = false;
+    return v;
+}
 static int next_loss_row() {
     static std::atomic<unsigned> n{0};
-    const int flag = g_loss_overwrite ? 256 : 0;
-    g_loss_overwrite = false;
+    const int flag = take_loss_overwrite() ? 256 : 0;
     return (int)(n.fetch_add(1) % LOSS_ROWS) | flag;
 }
 

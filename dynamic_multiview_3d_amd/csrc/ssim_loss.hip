@@ -1,0 +1,350 @@
+// SSIM as a training loss: loss = 1 - mean over images, windows and channels of the SSIM map S that mv3d_image_metrics averages
+// (metrics.hip: same 11 taps, same c1 / c2, same fp32 operation order up to S), and its gradient with respect to the prediction.
+//
+// Per window, with mx = F(a), my = F(b), sab = F(a b), s2 = F(a a + b b):
+//   A1 = 2 mx my + c1    B1 = mx^2 + my^2 + c1    A2 = 2 sab - 2 mx my + c2    B2 = s2 - (mx^2 + my^2) + c2    S = (A1/B1)(A2/B2)
+//   Dm = dS/dmx  = 2 (my (A2 - A1) - mx S (B2 - B1)) / (B1 B2)
+//   Ds = dS/dsab = 2 (A1/B1) / B2
+//   Dq = dS/ds2  = -S / B2
+//   dS_total/da(q) = Ft(Dm)(q) + b(q) Ft(Ds)(q) + 2 a(q) Ft(Dq)(q),    grad(q) = -weight / (N Hv Wv C) * dS_total/da(q)
+// Ft, the transpose of the valid window pass, is the same separable filter over the Hv x Wv map zero-padded by 10 on every
+// side (the window is symmetric).  The three coefficients are written so that a == b gives Dm == 0 and Ds == -2 Dq exactly.
+//
+// Built with -ffp-contract=off: every step is fp32 in the order of the numpy twin (metrics.py ssim_loss_host at float32): in both
+// directions the horizontal pass runs before the vertical one and taps are added in index order.  Only the sum of S is kept in
+// double, in a fixed order.
+//
+// Two launches, no atomics, no device state outside the caller's workspace:
+//   tile    one workgroup per 32x32 PIXEL tile of one image, so that every gradient element has exactly one writer.  Per channel
+//           it stages the 52x52 halo of a and b (origin 10 above and left of the tile, zeros outside the image), runs the
+//           forward horizontal pass (52 rows x 42 columns x 4 quantities) and the vertical pass: the 42x42 windows that touch the
+//           tile.  Each window's S, Dm, Ds, Dq are formed in registers (zero for a window outside [0,Hv) x [0,Wv)); S counts
+//           only for a window whose origin lies in the tile's own 32x32, so every window counts once.  The three coefficient maps
+//           go to LDS over the horizontal buffers, the transposed horizontal pass (42 x 32 x 3) overlays the staged images, and
+//           the transposed vertical pass ends with the combination at the pixel.  The forward pass is recomputed about
+//           (52/32)^2 = 2.6 times; in exchange the coefficient maps never travel through HBM.
+//   final   one workgroup adds the tile sums in a fixed order and adds (or stores) weight * (1 - sum / count) into loss_accum.
+//
+// LDS: staged rows are 53 floats apart, forward horizontal rows and coefficient rows 43, transposed horizontal rows 33: odd
+// pitches, because in the horizontal passes the lanes of a wave run down the rows.  2*52*53*4 + 4*52*43*4 = 57.8 KB static.
+#include "common.h"
+#include <cmath>
+
+namespace mv3d {
+namespace {
+
+constexpr int SL_TAPS = 11;
+constexpr int SL_PAD = SL_TAPS - 1;                // 10
+constexpr int SL_TILE = 32;                        // pixels per tile side
+constexpr int SL_WIN = SL_TILE + SL_PAD;           // 42 windows per side touch a tile
+constexpr int SL_HALO = SL_WIN + SL_PAD;           // 52 pixels per side feed them
+constexpr int SL_APITCH = SL_HALO + 1;             // 53
+constexpr int SL_HPITCH = SL_WIN + 1;              // 43
+constexpr int SL_TPITCH = SL_TILE + 1;             // 33
+constexpr int SL_HG = 3;                           // forward horizontal pass: columns per item (42 = 14 * 3)
+constexpr int SL_VR = 7;                           // forward vertical pass: rows per item (42 = 6 * 7; 42 * 6 = 252 items, one round)
+constexpr int SL_THREADS = 256;
+constexpr int SL_MAX_SIDE = 32768;
+
+static_assert(SL_WIN % SL_HG == 0 && SL_WIN % SL_VR == 0, "the forward passes cover the 42 windows without a remainder");
+static_assert(SL_WIN * (SL_WIN / SL_VR) <= SL_THREADS, "one vertical item per thread");
+static_assert(3 * SL_WIN * SL_TPITCH <= 2 * SL_HALO * SL_APITCH, "the transposed horizontal results fit over the staged images");
+static_assert(3 * SL_WIN * SL_HPITCH <= 4 * SL_HALO * SL_HPITCH, "the coefficient maps fit over the horizontal results");
+
+struct SlArgs {
+    const float* a; const float* b;
+    double* part; float* loss; float* grad;
+    int N, H, W, C, a_ld, b_ld, grad_ld, tx, ty, accumulate, overwrite;
+    float c1, c2, gscale, weight;
+    float w[SL_TAPS];
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs p) {
+    __shared__ float s_ab[2 * SL_HALO * SL_APITCH];        // a, b staged; later the transposed horizontal results
+    __shared__ float s_h[4 * SL_HALO * SL_HPITCH];         // forward horizontal results; later Dm, Ds, Dq
+    __shared__ double s_red[SL_THREADS / 64];
+    float* const s_a = s_ab;
+    float* const s_b = s_ab + SL_HALO * SL_APITCH;
+    const int tiles = p.tx * p.ty;
+    const int n = blockIdx.x / tiles, t = blockIdx.x - n * tiles;
+    const int y0 = (t / p.tx) * SL_TILE, x0 = (t % p.tx) * SL_TILE;
+    const int tid = threadIdx.x;
+    const int Hv = p.H - SL_PAD, Wv = p.W - SL_PAD;
+    const int64_t img = (int64_t)n * p.H * p.W;
+    const int px = tid & 31, py = (tid >> 5) * 4;          // this thread's 4 pixels: rows py .. py+3 of column px
+    const int wx = tid % SL_WIN, wy = (tid / SL_WIN) * SL_VR;      // its 7 windows: rows wy .. wy+6 of column wx (tid < 252)
+    double ssim = 0.0;
+
+    for (int c = 0; c < p.C; ++c) {
+        for (int i = tid; i < SL_HALO * SL_HALO; i += SL_THREADS) {
+            const int r = i / SL_HALO, q = i - r * SL_HALO;
+            const int y = y0 - SL_PAD + r, x = x0 - SL_PAD + q;
+            float va = 0.f, vb = 0.f;
+            if (y >= 0 && y < p.H && x >= 0 && x < p.W) {  // outside the image: zeros, which only reach windows that do not count
+                const int64_t pix = img + (int64_t)y * p.W + x;
+                va = p.a[pix * p.a_ld + c];
+                vb = p.b[pix * p.b_ld + c];
+            }
+            s_a[r * SL_APITCH + q] = va;
+            s_b[r * SL_APITCH + q] = vb;
+        }
+        __syncthreads();
+        float pa[4], pb[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            pa[o] = s_a[(py + o + SL_PAD) * SL_APITCH + px + SL_PAD];
+            pb[o] = s_b[(py + o + SL_PAD) * SL_APITCH + px + SL_PAD];
+        }
+        // forward horizontal pass: item = (row, group of 3 columns); lanes run down the rows
+        for (int i = tid; i < SL_HALO * (SL_WIN / SL_HG); i += SL_THREADS) {
+            const int cg = i / SL_HALO, r = i - cg * SL_HALO;
+            const float* ra = s_a + r * SL_APITCH + cg * SL_HG;
+            const float* rb = s_b + r * SL_APITCH + cg * SL_HG;
+            float acc[4][SL_HG] = {};
+#pragma unroll
+            for (int j = 0; j < SL_HG + SL_PAD; ++j) {
+                const float va = ra[j], vb = rb[j];
+                const float ab = va * vb, ss = va * va + vb * vb;
+#pragma unroll
+                for (int o = 0; o < SL_HG; ++o) {
+                    const int k = j - o;
+                    if (k >= 0 && k < SL_TAPS) {
+                        const float wk = p.w[k];
+                        acc[0][o] = acc[0][o] + wk * va;
+                        acc[1][o] = acc[1][o] + wk * vb;
+                        acc[2][o] = acc[2][o] + wk * ab;
+                        acc[3][o] = acc[3][o] + wk * ss;
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int o = 0; o < SL_HG; ++o) s_h[q * SL_HALO * SL_HPITCH + r * SL_HPITCH + cg * SL_HG + o] = acc[q][o];
+        }
+        __syncthreads();
+        // forward vertical pass: 7 rows of one window column per lane, then S and the three coefficients
+        float dm[SL_VR], ds[SL_VR], dq[SL_VR];
+        if (tid < SL_WIN * (SL_WIN / SL_VR)) {
+            float acc[4][SL_VR] = {};
+#pragma unroll
+            for (int j = 0; j < SL_VR + SL_PAD; ++j) {
+                float v[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = s_h[q * SL_HALO * SL_HPITCH + (wy + j) * SL_HPITCH + wx];
+#pragma unroll
+                for (int o = 0; o < SL_VR; ++o) {
+                    const int k = j - o;
+                    if (k >= 0 && k < SL_TAPS) {
+                        const float wk = p.w[k];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[q][o] = acc[q][o] + wk * v[q];
+                    }
+                }
+            }
+            const int ox = x0 - SL_PAD + wx;                              // window origin, image coordinates
+#pragma unroll
+            for (int o = 0; o < SL_VR; ++o) {
+                const int oy = y0 - SL_PAD + wy + o;
+                dm[o] = ds[o] = dq[o] = 0.f;
+                if (oy >= 0 && oy < Hv && ox >= 0 && ox < Wv) {
+                    const float mx = acc[0][o], my = acc[1][o], sab = acc[2][o], s2 = acc[3][o];
+                    const float num0 = (mx * my) * 2.0f, den0 = mx * mx + my * my;
+                    const float A1 = num0 + p.c1, B1 = den0 + p.c1;
+                    const float A2 = (sab * 2.0f - num0) + p.c2, B2 = (s2 - den0) + p.c2;
+                    const float lum = A1 / B1;
+                    const float cs = A2 / B2;
+                    const float S = lum * cs;
+                    dm[o] = ((my * (A2 - A1) - (mx * S) * (B2 - B1)) * 2.0f) / (B1 * B2);
+                    ds[o] = (lum / B2) * 2.0f;
+                    dq[o] = -(S / B2);
+                    if (oy >= y0 && ox >= x0) ssim += (double)S;           // origin in the tile's own 32x32: counted here and only here
+                }
+            }
+        }
+        __syncthreads();                                                   // every read of the horizontal results is done
+        if (!p.grad) continue;                                             // value only (uniform): the next barrier is the one after staging
+        float* const s_c = s_h;
+        if (tid < SL_WIN * (SL_WIN / SL_VR)) {
+#pragma unroll
+            for (int o = 0; o < SL_VR; ++o) {
+                const int at = (wy + o) * SL_HPITCH + wx;
+                s_c[at] = dm[o];
+                s_c[SL_WIN * SL_HPITCH + at] = ds[o];
+                s_c[2 * SL_WIN * SL_HPITCH + at] = dq[o];
+            }
+        }
+        __syncthreads();
+        // transposed horizontal pass: item = (window row, group of 4 pixel columns); lanes run down the rows
+        float* const s_t = s_ab;
+        for (int i = tid; i < SL_WIN * (SL_TILE / 4); i += SL_THREADS) {
+            const int cg = i / SL_WIN, r = i - cg * SL_WIN;
+            float acc[3][4] = {};
+#pragma unroll
+            for (int j = 0; j < 4 + SL_PAD; ++j) {
+                float v[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) v[q] = s_c[q * SL_WIN * SL_HPITCH + r * SL_HPITCH + cg * 4 + j];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    const int k = j - o;
+                    if (k >= 0 && k < SL_TAPS) {
+                        const float wk = p.w[k];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) acc[q][o] = acc[q][o] + wk * v[q];
+                    }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+                for (int o = 0; o < 4; ++o) s_t[q * SL_WIN * SL_TPITCH + r * SL_TPITCH + cg * 4 + o] = acc[q][o];
+        }
+        __syncthreads();
+        // transposed vertical pass: 4 rows of one pixel column per lane, then the combination at the pixel
+        {
+            float acc[3][4] = {};
+#pragma unroll
+            for (int j = 0; j < 4 + SL_PAD; ++j) {
+                float v[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) v[q] = s_t[q * SL_WIN * SL_TPITCH + (py + j) * SL_TPITCH + px];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    const int k = j - o;
+                    if (k >= 0 && k < SL_TAPS) {
+                        const float wk = p.w[k];
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) acc[q][o] = acc[q][o] + wk * v[q];
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const int y = y0 + py + o, x = x0 + px;
+                if (y < p.H && x < p.W) {
+                    const float g = ((acc[0][o] + pb[o] * acc[1][o]) + (pa[o] * 2.0f) * acc[2][o]) * p.gscale;
+                    float* dst = p.grad + (img + (int64_t)y * p.W + x) * p.grad_ld + c;
+                    *dst = p.accumulate ? *dst + g : g;
+                }
+            }
+        }
+        __syncthreads();                                                   // the staging of the next channel overwrites s_t
+    }
+
+    ssim = wave_sum(ssim);
+    if ((tid & 63) == 0) s_red[tid >> 6] = ssim;
+    __syncthreads();
+    if (tid == 0) p.part[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+__global__ __launch_bounds__(SL_THREADS) void ssim_loss_final_kernel(const SlArgs p) {
+    __shared__ double s_red[SL_THREADS / 64];
+    const int64_t total = (int64_t)p.N * p.tx * p.ty;
+    double s = 0.0;
+    for (int64_t t = threadIdx.x; t < total; t += SL_THREADS) s += p.part[t];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sum = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+        const double windows = (double)p.N * (double)(p.H - SL_PAD) * (double)(p.W - SL_PAD) * (double)p.C;
+        const float term = (float)((double)p.weight * (1.0 - sum / windows));
+        p.loss[0] = p.overwrite ? term : p.loss[0] + term;
+    }
+}
+
+// 0 when the shape is outside what the entry takes
+int64_t tile_count(int N, int H, int W, int C) {
+    if (N < 1 || H < SL_TAPS || W < SL_TAPS || C < 1 || C > 4 || H > SL_MAX_SIDE || W > SL_MAX_SIDE) return 0;
+    const int64_t total = (int64_t)N * cdiv(H, SL_TILE) * cdiv(W, SL_TILE);
+    return total <= INT32_MAX ? total : 0;
+}
+
+}  // namespace
+}  // namespace mv3d
+
+using namespace mv3d;
+
+extern "C" {
+
+size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C) {
+    const int64_t total = tile_count(N, H, W, C);
+    return (size_t)cdiv64(total * (int64_t)sizeof(double), 256) * 256;
+}
+
+int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
+                   void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    const char* fn = "mv3d_ssim_loss";
+    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
+    if (H < SL_TAPS) return fail(MV3D_E_INVAL, "%s: H (%d) smaller than the 11-tap window", fn, H);
+    if (W < SL_TAPS) return fail(MV3D_E_INVAL, "%s: W (%d) smaller than the 11-tap window", fn, W);
+    if (C < 1 || C > 4) return fail(MV3D_E_INVAL, "%s: C (%d) outside 1..4", fn, C);
+    if (H > SL_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: H (%d) above %d", fn, H, SL_MAX_SIDE);
+    if (W > SL_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: W (%d) above %d", fn, W, SL_MAX_SIDE);
+    const int64_t total = tile_count(N, H, W, C);
+    if (!total) return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d need 2^31 or more tiles", fn, N, H, W);
+    if (a_ld < C) return fail(MV3D_E_INVAL, "%s: a_ld (%d) smaller than C (%d)", fn, a_ld, C);
+    if (b_ld < C) return fail(MV3D_E_INVAL, "%s: b_ld (%d) smaller than C (%d)", fn, b_ld, C);
+    if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
+    if (grad_accumulate != 0 && grad_accumulate != 1) return fail(MV3D_E_INVAL, "%s: grad_accumulate (%d) must be 0 or 1", fn, grad_accumulate);
+    if (!std::isfinite(max_val) || !(max_val > 0.f)) return fail(MV3D_E_INVAL, "%s: max_val (%g) must be finite and positive", fn, (double)max_val);
+    if (!std::isfinite(weight)) return fail(MV3D_E_INVAL, "%s: weight (%g) must be finite", fn, (double)weight);
+    if (!a) return fail(MV3D_E_INVAL, "%s: a is null", fn);
+    if (!b) return fail(MV3D_E_INVAL, "%s: b is null", fn);
+    if (!loss_accum) return fail(MV3D_E_INVAL, "%s: loss_accum is null", fn);
+    if (!workspace) return fail(MV3D_E_INVAL, "%s: workspace is null", fn);
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)loss_accum | (uintptr_t)grad) & 3)
+        return fail(MV3D_E_INVAL, "%s: a, b, loss_accum or grad not 4-byte aligned", fn);
+    const size_t need = mv3d_ssim_loss_workspace_bytes(N, H, W, C);
+    if (workspace_bytes < need) return fail(MV3D_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(MV3D_E_WORKSPACE, "%s: workspace not 16-byte aligned", fn);
+
+    SlArgs p = {};
+    p.a = (const float*)a; p.b = (const float*)b; p.part = (double*)workspace; p.loss = (float*)loss_accum; p.grad = (float*)grad;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.a_ld = a_ld; p.b_ld = b_ld; p.grad_ld = grad_ld;
+    p.tx = cdiv(W, SL_TILE); p.ty = cdiv(H, SL_TILE);
+    p.accumulate = grad_accumulate;
+    p.overwrite = take_loss_overwrite() ? 1 : 0;          // mv3d_loss_overwrite_next(): consumed by this call, kept by a recorded one
+    p.weight = weight;
+    const double windows = (double)N * (double)(H - SL_PAD) * (double)(W - SL_PAD) * (double)C;
+    p.gscale = (float)(-(double)weight / windows);
+    // the constants of the numpy twin, rounded to fp32 once (as mv3d_image_metrics computes them)
+    const double k1 = 0.01 * (double)max_val, k2 = 0.03 * (double)max_val;
+    p.c1 = (float)(k1 * k1);
+    p.c2 = (float)(k2 * k2);
+    double g[SL_TAPS], sum = 0.0;
+    for (int k = 0; k < SL_TAPS; ++k) {
+        const double d = (double)(k - SL_TAPS / 2);
+        g[k] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
+        sum += g[k];
+    }
+    for (int k = 0; k < SL_TAPS; ++k) p.w[k] = (float)(g[k] / sum);
+
+    const double elems = (double)N * H * W * C;
+    // algorithmic bytes: both images once, the gradient written once (and read once when it accumulates), the tile sums written
+    // and read once.  FLOPs per element: 4 quantities x 2 passes x 11 taps x 2 forward, 3 x 2 x 11 x 2 transposed, ~40 for the
+    // window expression and the combination.
+    const double grad_bytes = grad ? (grad_accumulate ? 8.0 : 4.0) : 0.0;
+    const double flops = elems * (4.0 * 2 * SL_TAPS * 2 + (grad ? 3.0 * 2 * SL_TAPS * 2 + 40.0 : 12.0));
+    const OpInfo tile_info{intern_label("ssim_loss_tile"), flops, elems * (8.0 + grad_bytes) + (double)total * 8.0};
+    const int grid = (int)total;
+    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
+        ssim_loss_tile_kernel<<<grid, SL_THREADS, 0, s>>>(p);
+        return launched("ssim_loss_tile_kernel");
+    });
+    if (rc) return rc;
+    const OpInfo final_info{intern_label("ssim_loss_final"), 0.0, (double)total * 8.0 + 8.0};
+    return dispatch(stream, final_info, [=](hipStream_t s) {
+        ssim_loss_final_kernel<<<1, SL_THREADS, 0, s>>>(p);
+        return launched("ssim_loss_final_kernel");
+    });
+}
+
+}  // extern "C"

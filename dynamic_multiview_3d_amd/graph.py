@@ -183,9 +183,18 @@ class ScalarExpr:
     __rmul__ = __mul__
 
 
+LOSS_L1, LOSS_L2, LOSS_SSIM = 1, 2, 3
+
+
 class LossTerm:
-    def __init__(self, a, b, kind, mask=None, b_scale=1.0):
+    """One term of the loss on the differentiated tensor a against b.  kind LOSS_L1 / LOSS_L2: the pixel losses (mv3d_pixel_loss*),
+    with an optional one-channel mask and a scale on b.  kind LOSS_SSIM: 1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss);
+    no mask, no scale.  `ws` is an SSIM term's own workspace, allocated by Graph.compile()."""
+
+    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0):
         self.a, self.b, self.kind, self.mask, self.b_scale = a, b, kind, mask, float(b_scale)
+        self.max_val = float(max_val)
+        self.ws = None
 
 
 # =============================================================================================== nodes
@@ -721,6 +730,8 @@ class Graph:
             if len(uses) != 1:
                 continue
             w, t = uses[0]
+            if t.kind == LOSS_SSIM:
+                continue            # the SSIM loss needs gen and writes its gradient in HBM: it never fuses
             if t.a is not gen or t.mask is not None or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
                 continue
             if gen.C > 4 or gen.ld != gen.C or gen.storage.has_alias or gen.storage.alias_of is not None:
@@ -780,17 +791,27 @@ class Graph:
     def _emit_losses(self, with_grad):
         if self.loss_expr is None:
             return
-        for w, term in self.loss_expr.terms:
+        # A pixel loss stores its gradient, the SSIM loss can add to one: the pixel terms go first, and an SSIM term accumulates
+        # when an earlier term of this step has written the gradient of the same tensor (L2 + SSIM on one prediction).
+        written = set()             # gradient addresses written by the terms so far
+        terms = [wt for wt in self.loss_expr.terms if wt[1].kind != LOSS_SSIM] + [wt for wt in self.loss_expr.terms if wt[1].kind == LOSS_SSIM]
+        for w, term in terms:
             if id(term) in self.fused_terms:
                 continue
             a, b, m = term.a, term.b, term.mask
             if a.C != b.C or a.rows != b.rows:
                 raise ValueError("loss operands of different shapes")
             grad = a.grad_ptr if (with_grad and a.requires_grad) else None
-            self.lib.pixel_loss_strided(a.rows, a.C, a.ptr, a.ld, b.ptr, b.ld, term.b_scale,
-                                        m.ptr if m is not None else None, m.ld if m is not None else 1,
-                                        term.kind, float(w), self.loss_buf.data_ptr(), grad, a.ld, self.stream)
+            if term.kind == LOSS_SSIM:
+                n, h, wd, c = a.shape
+                self.lib.ssim_loss(n, h, wd, c, a.ptr, a.ld, b.ptr, b.ld, term.max_val, float(w), self.loss_buf.data_ptr(), grad, a.ld,
+                                   1 if grad in written else 0, term.ws.data_ptr(), term.ws.numel(), self.stream)
+            else:
+                self.lib.pixel_loss_strided(a.rows, a.C, a.ptr, a.ld, b.ptr, b.ld, term.b_scale,
+                                            m.ptr if m is not None else None, m.ld if m is not None else 1,
+                                            term.kind, float(w), self.loss_buf.data_ptr(), grad, a.ld, self.stream)
             if grad is not None:
+                written.add(grad)
                 _note_grad_written(a, False)
 
     def compile(self, stream=None):
@@ -802,6 +823,14 @@ class Graph:
             t.grad_written = t.grad_masked = False
         self._bind_prepared_filters()
         self._fuse_resample_losses()
+        # every SSIM term keeps its per-tile sums in a workspace of its own (not the shared scratch: the term's two launches must
+        # find it untouched whatever runs beside them)
+        for _, term in (self.loss_expr.terms if self.loss_expr is not None else ()):
+            if term.kind == LOSS_SSIM and term.ws is None:
+                nbytes = int(lib.ssim_loss_workspace_bytes(*term.a.shape))
+                if not nbytes:
+                    raise ValueError("ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (term.a.shape,))
+                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._find_fc_chains()
         self.plan_fwd = lib.plan_create()
         lib.plan_begin(self.plan_fwd)

@@ -11,6 +11,8 @@ from .model_base import ModelBase, optimizer_from_conf
 
 
 class Base_Prediction_Model(ModelBase):
+    supports_ssim_loss = True
+
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
         self.batch_size = conf['batch_size']
@@ -107,6 +109,7 @@ class Base_Prediction_Model(ModelBase):
         self.loss = 0.
         if 'use_color' in self.conf:
             self.loss += euclidean_loss(self.gen_image1, self.image1)
+            self.loss += self.ssim_term(self.gen_image1, self.image1)      # conf['ssim_loss_weight']; the depth term stays L2
         if 'use_depth' in self.conf:
             self.loss += euclidean_loss(self.gen_dimage1, self.dimage1) * self.conf['depth_lr_factor']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)

@@ -47,9 +47,8 @@ def _valid_filter(x, w):
     return v
 
 
-def ssim_map(a, b, max_val, dtype=np.float64):
-    """lum * cs at every fully-inside window: [N, H-10, W-10, C] in `dtype` arithmetic."""
-    dtype = np.dtype(dtype).type
+def _ssim_operands(a, b, max_val, dtype):
+    """The operand checks of the SSIM functions: (a, b) in `dtype` and max_val as the float the C ABI takes."""
     a, b = np.asarray(a).astype(dtype), np.asarray(b).astype(dtype)
     if a.shape != b.shape or a.ndim != 4:
         raise ValueError("ssim: operands must be [N,H,W,C] of one shape, got %s and %s" % (a.shape, b.shape))
@@ -58,6 +57,18 @@ def ssim_map(a, b, max_val, dtype=np.float64):
     max_val = float(np.float32(max_val))                     # the C ABI takes a float
     if not math.isfinite(max_val) or max_val <= 0:
         raise ValueError("ssim: max_val must be finite and positive")
+    return a, b, max_val
+
+
+def ssim_map(a, b, max_val, dtype=np.float64):
+    """lum * cs at every fully-inside window: [N, H-10, W-10, C] in `dtype` arithmetic."""
+    dtype = np.dtype(dtype).type
+    a, b, max_val = _ssim_operands(a, b, max_val, dtype)
+    return _ssim_parts(a, b, max_val, dtype)[-1]
+
+
+def _ssim_parts(a, b, max_val, dtype):
+    """(mx, my, A1, B1, A2, B2, lum, S = lum * cs) of the SSIM expression, each [N, H-10, W-10, C] in `dtype`."""
     k1, k2 = K1 * max_val, K2 * max_val
     c1, c2 = dtype(k1 * k1), dtype(k2 * k2)
     w = ssim_window(dtype)
@@ -67,9 +78,45 @@ def ssim_map(a, b, max_val, dtype=np.float64):
     s2 = _valid_filter(a * a + b * b, w)
     num0 = (mx * my) * two
     den0 = mx * mx + my * my
-    lum = (num0 + c1) / (den0 + c1)
-    cs = ((sab * two - num0) + c2) / ((s2 - den0) + c2)
-    return lum * cs
+    A1, B1 = num0 + c1, den0 + c1
+    A2, B2 = (sab * two - num0) + c2, (s2 - den0) + c2
+    lum = A1 / B1
+    cs = A2 / B2
+    return mx, my, A1, B1, A2, B2, lum, lum * cs
+
+
+def _transposed_filter(d, w):
+    """Ft over [N,Hv,Wv,C]: the transpose of _valid_filter.  The window is symmetric, so it is the same pass (horizontal, then
+    vertical, taps added in index order) over the map zero-padded by taps-1 on every side; the result is [N,Hv+10,Wv+10,C]."""
+    pad = len(w) - 1
+    n, hv, wv, c = d.shape
+    p = np.zeros((n, hv + 2 * pad, wv + 2 * pad, c), d.dtype)
+    p[:, pad:pad + hv, pad:pad + wv] = d
+    return _valid_filter(p, w)
+
+
+def ssim_loss_host(pred, target, max_val=1.0, dtype=np.float64, weight=1.0):
+    """(loss, grad): loss = weight * (1 - mean of ssim_map over images, windows and channels), a scalar of `dtype`, and grad =
+    d loss / d pred, [N,H,W,C] in `dtype`; every step in `dtype` arithmetic.  At float32 this states mv3d_ssim_loss's own
+    operation order (csrc/ssim_loss.hip); only the sum behind the mean differs (the kernel keeps it in double).
+
+    Per window:  Dm = dS/dmx = 2 (my (A2 - A1) - mx S (B2 - B1)) / (B1 B2),  Ds = dS/dsab = 2 lum / B2,  Dq = dS/ds2 = -S / B2
+    grad = -weight / count * (Ft(Dm) + target * Ft(Ds) + 2 pred * Ft(Dq));  pred == target gives exactly (0, zeros)."""
+    dtype = np.dtype(dtype).type
+    a, b, max_val = _ssim_operands(pred, target, max_val, dtype)
+    weight = float(np.float32(weight))                       # the C ABI takes a float
+    if not math.isfinite(weight):
+        raise ValueError("ssim_loss: weight must be finite")
+    w = ssim_window(dtype)
+    two = dtype(2)
+    mx, my, A1, B1, A2, B2, lum, S = _ssim_parts(a, b, max_val, dtype)
+    count = S.size
+    loss = dtype(weight * float(dtype(1) - S.mean(dtype=dtype)))
+    dm = ((my * (A2 - A1) - (mx * S) * (B2 - B1)) * two) / (B1 * B2)
+    ds = (lum / B2) * two
+    dq = -(S / B2)
+    g = (_transposed_filter(dm, w) + b * _transposed_filter(ds, w)) + (a * two) * _transposed_filter(dq, w)
+    return loss, g * dtype(-weight / count)
 
 
 def image_metrics_host(pred, target, max_val=1.0, dtype=np.float64):
@@ -156,4 +203,38 @@ def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
     if stream is None:
         stream = torch.cuda.current_stream(out.device).cuda_stream
     lib.image_metrics(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), out.data_ptr(), ws.data_ptr(), nbytes, stream)
+    return out
+
+
+def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False, stream=None):
+    """mv3d_ssim_loss on device memory: weight * (1 - mean SSIM) of pred against target, and optionally its gradient with
+    respect to pred.  pred / target: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with
+    the operand rules of image_metrics.  grad: an optional float32 device tensor of pred's shape with one pixel stride (a
+    channel slice of a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream`
+    (default: torch's current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
+    import torch
+    from . import _lib
+    pa, shape, a_ld, dev = _operand(pred, 'pred')
+    pb, shape_b, b_ld, dev_b = _operand(target, 'target')
+    if shape != shape_b:
+        raise ValueError("ssim_loss: pred %s and target %s differ in shape" % (shape, shape_b))
+    dev = torch.device(dev)
+    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
+        raise _lib.Mv3dError("ssim_loss runs on the GPU (operands are on %s); ssim_loss_host is the numpy form" % dev)
+    n, h, w, c = shape
+    pg, g_ld = None, c
+    if grad is not None:
+        if not torch.is_tensor(grad):
+            raise ValueError("ssim_loss: grad must be a torch device tensor")
+        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
+        if shape_g != shape or torch.device(dev_g) != dev:
+            raise ValueError("ssim_loss: grad %s on %s does not match pred %s on %s" % (shape_g, dev_g, shape, dev))
+    out = torch.zeros((), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    nbytes = int(lib.ssim_loss_workspace_bytes(n, h, w, c))
+    ws = _workspace(dev, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.ssim_loss(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld, 1 if accumulate else 0,
+                  ws.data_ptr(), nbytes, stream)
     return out

@@ -100,10 +100,41 @@ def optimizer_from_conf(conf, learning_rate, **adam_kw):
     raise ValueError("unknown conf['optimizer'] %r (have 'adam', 'momentum', 'sgd')" % (name,))
 
 
+def ssim_weight_from_conf(conf):
+    """conf['ssim_loss_weight'] as a float: 0.0 when the key is absent (or None), which leaves the loss as the reference
+    defines it.  Raises ValueError on a negative or non-finite value, before any device work."""
+    w = conf.get('ssim_loss_weight')
+    if w is None:
+        return 0.0
+    w = float(w)
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("conf['ssim_loss_weight'] must be finite and >= 0, got %r" % (conf['ssim_loss_weight'],))
+    return w
+
+
 class ModelBase(object):
     input_names = ()
+    supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() set it
+
+    def _check_conf(self):
+        """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
+        if ssim_weight_from_conf(self.conf) > 0 and not self.supports_ssim_loss:
+            raise ValueError("%s does not support conf['ssim_loss_weight']" % type(self).__name__)
+
+    def ssim_term(self, pred, target):
+        """conf['ssim_loss_weight'] * ssim_loss(pred, target, max_val) with max_val from this model's eval_pairs() entry of the
+        pair, or 0 when the switch is absent or 0 (the graph then records exactly what it recorded without the key)."""
+        from .tf_utils import ssim_loss
+        w = ssim_weight_from_conf(self.conf)
+        if w == 0:
+            return 0
+        for _, p, t, max_val in self.eval_pairs():
+            if p is pred and t is target:
+                return ssim_loss(pred, target, max_val) * w
+        raise RuntimeError("ssim_term: eval_pairs() of %s has no entry for this pair" % type(self).__name__)
 
     def _make_graph(self, device, seed):
+        self._check_conf()
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 

@@ -16,6 +16,7 @@ INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3)
 
 
 class MultiObjectAppFlow(ModelBase):
+    supports_ssim_loss = True
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
         self.batch_size = conf['batch_size']
@@ -163,6 +164,7 @@ class MultiObjectAppFlow(ModelBase):
             colorloss = 0.
             if 'combination_image' in self.conf:
                 colorloss += euclidean_loss(self.gen_image1, self.image1)
+                colorloss += self.ssim_term(self.gen_image1, self.image1)      # conf['ssim_loss_weight']; every other term stays L2
             if 'gen_sep_images' in self.conf:
                 if 'masked_image_loss' in self.conf:
                     colorloss += masked_euclidean_loss(self.gen_image1_only0, self.image1_only0, self.image1_mask0)

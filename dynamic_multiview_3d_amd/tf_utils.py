@@ -7,7 +7,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, ConvNode, LinearNode, ActNode, ViewNode,
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, ConvNode, LinearNode, ActNode, ViewNode,
                     CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
@@ -97,6 +97,28 @@ def masked_euclidean_loss(input1, input2, mask):
     """reduce_mean(reduce_sum(pow((a-b)*mask, 2), 3)) -- the inline expression of
     multi_view_model/multiobject_appflow.py:239-242 (mask is [B,H,W,1])."""
     return _loss_term(input1, input2, 2, mask)
+
+
+def ssim_loss(input1, input2, max_val=1.0):
+    """1 - reduce_mean(tf.image.ssim(a, b, max_val)) for images of one size: the mean over images, fully-inside 11x11 Gaussian
+    windows and channels (mv3d_ssim_loss; metrics.py states the definition).  Operands [N,H,W,C] with H, W >= 11 and C <= 4;
+    exactly one of them is differentiated.  Masked and scaled operands are not supported."""
+    for v in (input1, input2):
+        if isinstance(v, (_Masked, _Scaled)):
+            raise NotImplementedError("ssim_loss of a masked or scaled operand")
+    a, b = input1, input2
+    # the differentiated operand goes first; SSIM is symmetric in its arguments
+    if b.requires_grad and not a.requires_grad:
+        a, b = b, a
+    elif a.requires_grad and b.requires_grad:
+        raise NotImplementedError("loss between two differentiated tensors")
+    if len(a.shape) != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("ssim_loss: operands must be [N,H,W,C] of one shape, got %s and %s" % (a.shape, b.shape))
+    if a.shape[1] < 11 or a.shape[2] < 11 or a.C > 4:
+        raise ValueError("ssim_loss: needs H, W >= 11 and C <= 4, got %s" % (a.shape,))
+    if not (math.isfinite(float(max_val)) and float(max_val) > 0):
+        raise ValueError("ssim_loss: max_val must be finite and positive")
+    return ScalarExpr([(1.0, LossTerm(a, b, LOSS_SSIM, max_val=max_val))])
 
 
 # ------------------------------------------------------------------------------------------------ activations

@@ -237,7 +237,8 @@ int mv3d_resampler_bwd(int N, int P, int Hs, int Ws, int C, const void* data, in
 
 /* ---- losses: euclidean_loss / l1_loss (tf_utils.py:18-23) -----------------------------------
  * loss_accum[0] += weight * mean_{n,h,w} sum_c f((a-b)*mask);  grad (optional, same shape as a,
- * dense) = d(weight*loss)/da.  kind 2 = squared (euclidean), 1 = absolute (l1).  mask (optional)
+ * dense) = d(weight*loss)/da.  kind 2 = squared (euclidean), 1 = absolute (l1); the third kind of loss term, SSIM, has its
+ * own entry point (mv3d_ssim_loss below).  mask (optional)
  * is [pixels,1] and multiplies the difference (multiobject_appflow.py:239-242).
  * loss_accum must be zeroed by the caller before the first term (mv3d_fill). */
 int mv3d_pixel_loss(int64_t pixels, int ch, const void* a, const void* b, const void* mask, int kind, float weight,
@@ -249,7 +250,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -276,6 +277,36 @@ int mv3d_loss_overwrite_next(void);
 size_t mv3d_image_metrics_workspace_bytes(int N, int H, int W, int C);
 int mv3d_image_metrics(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, void* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- SSIM as a training loss: value and gradient with respect to the prediction ---------------------------------------
+ * a (prediction), b (target) [N,H,W,C] fp32 with pixel strides a_ld / b_ld (channel-slice views work), C in 1..4; Hv = H - 10,
+ * Wv = W - 10.  With S = lum * cs the SSIM map of mv3d_image_metrics above (same window, c1, c2 and fp32 operation order):
+ *   ssim_loss = 1 - (1 / (N*Hv*Wv*C)) * sum over images, windows and channels of S
+ *             = 1 - the mean over the images of out[n][2] of mv3d_image_metrics;
+ *   loss_accum[0] += weight * ssim_loss, or = weight * ssim_loss when mv3d_loss_overwrite_next() is pending on the calling thread
+ *   (the flag is consumed; a recorded call keeps what it saw).  One thread adds, in stream order: no atomics.
+ * grad (optional; NULL = value only) [N,H,W,C] with pixel stride grad_ld >= C receives d(weight * ssim_loss)/da: stored when
+ * grad_accumulate == 0, added to what is there when grad_accumulate == 1 (a second differentiated term on one tensor).  Channels
+ * outside the view are not touched.  Per window, with mx = F(a), my = F(b), sab = F(a b), s2 = F(a a + b b):
+ *   A1 = 2 mx my + c1,  B1 = mx^2 + my^2 + c1,  A2 = 2 sab - 2 mx my + c2,  B2 = s2 - (mx^2 + my^2) + c2,  S = (A1/B1)(A2/B2)
+ *   Dm = 2 (my (A2 - A1) - mx S (B2 - B1)) / (B1 B2)      Ds = 2 (A1/B1) / B2      Dq = -S / B2
+ *   grad(q) = -weight / (N*Hv*Wv*C) * (Ft(Dm)(q) + b(q) Ft(Ds)(q) + 2 a(q) Ft(Dq)(q))
+ * where Ft, the transpose of the valid window pass, is the same separable 11-tap filter over the Hv x Wv map zero-padded by
+ * 10 on every side.  The window passes (horizontal first, taps added in index order, in both directions), S, the coefficients
+ * and the combination are fp32 without contraction: the numbers metrics.py ssim_loss_host computes in float32.  The sum of S is
+ * kept in double and reduced in a fixed order.  a == b gives a loss of exactly 0 and a gradient of exactly 0.
+ * Every gradient element is written by exactly one thread; the same inputs give the same bits in value and gradient, run after
+ * run and under plan replay; the value is the same bits with and without grad.  The call allocates nothing and keeps no state
+ * outside `workspace` (16-byte aligned, mv3d_ssim_loss_workspace_bytes() bytes, which is 0 for a shape the entry refuses): the
+ * per-tile sums live there between its two launches (plan labels ssim_loss_tile, ssim_loss_final).
+ * MV3D_E_INVAL before any launch: N < 1; H or W < 11; C outside 1..4; H or W > 32768, or N * ceil(H/32) * ceil(W/32) >= 2^31;
+ * a_ld or b_ld < C; grad given and grad_ld < C; grad_accumulate outside {0, 1}; max_val not finite or <= 0; weight not finite;
+ * a, b, loss_accum or workspace null; a, b, loss_accum or grad not 4-byte aligned.  MV3D_E_WORKSPACE: workspace too small or not
+ * 16-byte aligned.  On any error loss_accum and grad are left untouched and a pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C);
+int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
+                   void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
+                   void* stream);
 
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
