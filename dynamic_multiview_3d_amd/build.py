@@ -24,6 +24,7 @@ UNITS = {
     "process_image.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
     "ssim_loss.hip": ["-ffp-contract=off"],
+    "flow_smooth.hip": ["-ffp-contract=off"],
     "comm.hip": [],                     # RCCL resolved at run time (dlsym): no link-time dependency
     "tfrecord.hip": ["-msse4.2"],       # host code only: the input thread's record reader (hardware crc32c)
 }

@@ -1,0 +1,319 @@
+// Edge-aware first-order smoothness of a two-channel flow field: value and gradient with respect to the flow.
+//
+//   dx[n,i,j,c] = f[n,i,j+1,c] - f[n,i,j,c]  (j < W-1)        dy[n,i,j,c] = f[n,i+1,j,c] - f[n,i,j,c]  (i < H-1)
+//   wx[n,i,j]   = exp(-(alpha/Cg) * sum_k |I[n,i,j+1,k] - I[n,i,j,k]|),  wy the same along rows;  1 without a guide
+//   phi(d) = sqrt(d^2 + eps^2) - eps  (Charbonnier)            phi'(d) = d / sqrt(d^2 + eps^2)
+//   S = sum wx phi(dx) / Zx + sum wy phi(dy) / Zy,   Zx = N H (W-1) 2,   Zy = N (H-1) W 2
+//   dS/df[n,i,j,c] = (ex[i,j-1] - ex[i,j]) / Zx + (ey[i-1,j] - ey[i,j]) / Zy,   ex = wx phi'(dx),  ey = wy phi'(dy),  0 out of range
+//
+// Built with -ffp-contract=off: every step is fp32 in the order of the numpy twin (metrics.py flow_smoothness_host at float32),
+// up to expf.  sqrt and the division are the correctly rounded ones, so sqrt(eps * eps) == eps: a constant flow gives d == 0,
+// phi == 0 and phi' == 0 exactly, whatever the guide.  Only the two sums behind S are kept in double, in a fixed order.
+//
+// Two launches, no atomics, no device state outside the caller's workspace:
+//   tile    one workgroup of 256 threads per 16 x 64 pixel tile of one image (a wave covers one 64-pixel row: 512 contiguous
+//           bytes of a dense flow).  It stages the 18 x 66 halo of the flow (as float2) and of the guide's channels (one plane
+//           each) in LDS, zeros outside the image.  Then every edge the tile's pixels touch is evaluated ONCE: 16 x 65 horizontal
+//           edges (origins one column left of the tile up to its last column) and 17 x 64 vertical ones; an edge's weight, its
+//           root, phi and phi' serve both channels and both pixels it joins.  ex / ey go to LDS; phi counts in the value only for
+//           an edge whose ORIGIN pixel lies in the tile, so every difference counts once.  Last, every pixel combines its four
+//           edges and writes (or adds to) its two gradient channels: one writer per element.
+//   final   one workgroup adds the tiles' two sums in a fixed order and adds (or stores) weight * S into loss_accum.
+// A call without loss_accum skips the sums and the final launch; one without grad skips ex / ey and the last phase.
+//
+// LDS: lanes run along the columns in every phase (consecutive float2 / float addresses), so no pitch needs padding against the
+// 64 banks.  9.5 KB flow halo + 4.75 KB per guide channel + 8.3 KB ex + 8.7 KB ey: 26.5 KB unguided, 45.5 KB with four channels.
+#include "common.h"
+#include <cmath>
+
+namespace mv3d {
+namespace {
+
+constexpr int FS_TW = 64;                          // tile width in pixels: one wave per row
+constexpr int FS_TH = 16;                          // tile height
+constexpr int FS_HW = FS_TW + 2;                   // halo width
+constexpr int FS_HH = FS_TH + 2;                   // halo height
+constexpr int FS_THREADS = 256;
+constexpr int FS_ROWS = FS_TH / (FS_THREADS / FS_TW);      // pixel rows per thread in the last phase (4)
+
+static_assert(FS_THREADS % FS_TW == 0 && FS_TH % (FS_THREADS / FS_TW) == 0, "the last phase covers the tile without a remainder");
+
+struct FsArgs {
+    const float* flow; const float* guide;
+    double* part; float* loss; float* grad;
+    int N, H, W, flow_ld, guide_ld, grad_ld, tx, ty, accumulate, overwrite, flow_vec, guide_vec, grad_vec;
+    float alpha_c, eps, eps2, cx, cy, weight;
+    double zx, zy;
+};
+
+__device__ __forceinline__ double fs_wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// one edge of one channel: d the difference, w the edge weight.  e = w * phi'(d); returns w * phi(d).
+__device__ __forceinline__ float fs_edge(float d, float w, float eps, float eps2, float& e) {
+    const float r = sqrtf(d * d + eps2);               // plain sqrtf and / are the correctly rounded ones (the __f*_rn forms map to the
+    e = w * (d / r);                                    // native 1-ulp root here); tests/test_gpu_flow_smooth.py holds the kernel to that
+    return w * (r - eps);
+}
+
+template <int GC>
+__global__ __launch_bounds__(FS_THREADS) void flow_smooth_tile_kernel(const FsArgs p) {
+    __shared__ float2 s_f[FS_HH * FS_HW];
+    __shared__ float s_g[(GC ? GC : 1) * FS_HH * FS_HW];
+    __shared__ float2 s_ex[FS_TH * (FS_TW + 1)];            // [r][q]: the edge with origin (y0 + r, x0 - 1 + q)
+    __shared__ float2 s_ey[(FS_TH + 1) * FS_TW];            // [r][q]: the edge with origin (y0 - 1 + r, x0 + q)
+    __shared__ double s_red[2 * (FS_THREADS / 64)];
+    const int tiles = p.tx * p.ty;
+    const int n = blockIdx.x / tiles, t = blockIdx.x - n * tiles;
+    const int y0 = (t / p.tx) * FS_TH, x0 = (t % p.tx) * FS_TW;
+    const int tid = threadIdx.x;
+    const int64_t img = (int64_t)n * p.H * p.W;
+
+    for (int i = tid; i < FS_HH * FS_HW; i += FS_THREADS) {
+        const int r = i / FS_HW, q = i - r * FS_HW;
+        const int y = y0 - 1 + r, x = x0 - 1 + q;
+        float2 f = make_float2(0.f, 0.f);
+        float g[GC ? GC : 1] = {};
+        if (y >= 0 && y < p.H && x >= 0 && x < p.W) {       // outside the image: zeros, which only reach edges that are dropped
+            const int64_t pix = img + (int64_t)y * p.W + x;
+            const float* src = p.flow + pix * p.flow_ld;
+            if (p.flow_vec) f = *reinterpret_cast<const float2*>(src);
+            else { f.x = src[0]; f.y = src[1]; }
+            if (GC) {
+                const float* gs = p.guide + pix * p.guide_ld;
+                bool done = false;
+                if constexpr (GC == 4) {
+                    if (p.guide_vec) {
+                        const float4 v = *reinterpret_cast<const float4*>(gs);
+                        g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
+                        done = true;
+                    }
+                }
+                if constexpr (GC == 2) {
+                    if (p.guide_vec) {
+                        const float2 v = *reinterpret_cast<const float2*>(gs);
+                        g[0] = v.x; g[1] = v.y;
+                        done = true;
+                    }
+                }
+                if (!done) {
+#pragma unroll
+                    for (int k = 0; k < GC; ++k) g[k] = gs[k];
+                }
+            }
+        }
+        s_f[i] = f;
+#pragma unroll
+        for (int k = 0; k < GC; ++k) s_g[k * FS_HH * FS_HW + i] = g[k];
+    }
+    __syncthreads();
+
+    const bool want_value = p.loss != nullptr, want_grad = p.grad != nullptr;
+    double sx = 0.0, sy = 0.0;
+    // horizontal edges: halo row r + 1, between halo columns q and q + 1
+    for (int i = tid; i < FS_TH * (FS_TW + 1); i += FS_THREADS) {
+        const int r = i / (FS_TW + 1), q = i - r * (FS_TW + 1);
+        const int y = y0 + r, x = x0 - 1 + q;
+        float2 e = make_float2(0.f, 0.f);
+        if (y < p.H && x >= 0 && x + 1 < p.W) {
+            const int at = (r + 1) * FS_HW + q;
+            const float2 f0 = s_f[at], f1 = s_f[at + 1];
+            float w = 1.0f;
+            if (GC) {
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < GC; ++k) s = s + fabsf(s_g[k * FS_HH * FS_HW + at + 1] - s_g[k * FS_HH * FS_HW + at]);
+                w = expf(-(p.alpha_c * s));
+            }
+            const float v0 = fs_edge(f1.x - f0.x, w, p.eps, p.eps2, e.x);
+            const float v1 = fs_edge(f1.y - f0.y, w, p.eps, p.eps2, e.y);
+            if (q >= 1) sx += (double)v0 + (double)v1;          // origin in the tile: counted here and only here
+        }
+        if (want_grad) s_ex[i] = e;
+    }
+    // vertical edges: halo column q + 1, between halo rows r and r + 1
+    for (int i = tid; i < (FS_TH + 1) * FS_TW; i += FS_THREADS) {
+        const int r = i / FS_TW, q = i - r * FS_TW;
+        const int y = y0 - 1 + r, x = x0 + q;
+        float2 e = make_float2(0.f, 0.f);
+        if (x < p.W && y >= 0 && y + 1 < p.H) {
+            const int at = r * FS_HW + q + 1;
+            const float2 f0 = s_f[at], f1 = s_f[at + FS_HW];
+            float w = 1.0f;
+            if (GC) {
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < GC; ++k) s = s + fabsf(s_g[k * FS_HH * FS_HW + at + FS_HW] - s_g[k * FS_HH * FS_HW + at]);
+                w = expf(-(p.alpha_c * s));
+            }
+            const float v0 = fs_edge(f1.x - f0.x, w, p.eps, p.eps2, e.x);
+            const float v1 = fs_edge(f1.y - f0.y, w, p.eps, p.eps2, e.y);
+            if (r >= 1) sy += (double)v0 + (double)v1;
+        }
+        if (want_grad) s_ey[i] = e;
+    }
+
+    if (want_value) {
+        sx = fs_wave_sum(sx);
+        sy = fs_wave_sum(sy);
+        if ((tid & 63) == 0) { s_red[tid >> 6] = sx; s_red[FS_THREADS / 64 + (tid >> 6)] = sy; }
+    }
+    __syncthreads();
+    if (want_value && tid == 0) {
+        p.part[2 * (int64_t)blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+        p.part[2 * (int64_t)blockIdx.x + 1] = ((s_red[4] + s_red[5]) + s_red[6]) + s_red[7];
+    }
+    if (!want_grad) return;
+
+    const int px = tid & (FS_TW - 1), x = x0 + px;
+    if (x >= p.W) return;
+#pragma unroll
+    for (int o = 0; o < FS_ROWS; ++o) {
+        const int pr = (tid / FS_TW) + o * (FS_THREADS / FS_TW), y = y0 + pr;
+        if (y >= p.H) break;
+        const float2 el = s_ex[pr * (FS_TW + 1) + px], er = s_ex[pr * (FS_TW + 1) + px + 1];
+        const float2 eu = s_ey[pr * FS_TW + px], ed = s_ey[(pr + 1) * FS_TW + px];
+        float2 g;
+        g.x = (el.x - er.x) * p.cx + (eu.x - ed.x) * p.cy;
+        g.y = (el.y - er.y) * p.cx + (eu.y - ed.y) * p.cy;
+        float* dst = p.grad + (img + (int64_t)y * p.W + x) * p.grad_ld;
+        if (p.grad_vec) {
+            float2* d2 = reinterpret_cast<float2*>(dst);
+            if (p.accumulate) { const float2 old = *d2; g.x = old.x + g.x; g.y = old.y + g.y; }
+            *d2 = g;
+        } else {
+            if (p.accumulate) { g.x = dst[0] + g.x; g.y = dst[1] + g.y; }
+            dst[0] = g.x;
+            dst[1] = g.y;
+        }
+    }
+}
+
+__global__ __launch_bounds__(FS_THREADS) void flow_smooth_final_kernel(const FsArgs p) {
+    __shared__ double s_red[2 * (FS_THREADS / 64)];
+    const int64_t total = (int64_t)p.N * p.tx * p.ty;
+    double sx = 0.0, sy = 0.0;
+    for (int64_t t = threadIdx.x; t < total; t += FS_THREADS) { sx += p.part[2 * t]; sy += p.part[2 * t + 1]; }
+    sx = fs_wave_sum(sx);
+    sy = fs_wave_sum(sy);
+    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = sx; s_red[FS_THREADS / 64 + (threadIdx.x >> 6)] = sy; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double tx = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+        const double ty = ((s_red[4] + s_red[5]) + s_red[6]) + s_red[7];
+        const float term = (float)((double)p.weight * (tx / p.zx + ty / p.zy));
+        p.loss[0] = p.overwrite ? term : p.loss[0] + term;
+    }
+}
+
+// 0 when the shape is outside what the entry takes
+int64_t fs_tile_count(int N, int H, int W) {
+    if (N < 1 || H < 2 || W < 2) return 0;
+    const int64_t total = (int64_t)N * cdiv(H, FS_TH) * cdiv(W, FS_TW);
+    return total <= INT32_MAX ? total : 0;
+}
+
+template <int GC>
+int fs_launch_tile(const FsArgs& p, int grid, hipStream_t s) {
+    flow_smooth_tile_kernel<GC><<<grid, FS_THREADS, 0, s>>>(p);
+    return launched("flow_smooth_tile_kernel");
+}
+
+}  // namespace
+}  // namespace mv3d
+
+using namespace mv3d;
+
+extern "C" {
+
+size_t mv3d_flow_smoothness_workspace_bytes(int N, int H, int W) {
+    const int64_t total = fs_tile_count(N, H, W);
+    return (size_t)cdiv64(total * 2 * (int64_t)sizeof(double), 256) * 256;
+}
+
+int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
+                         float edge_alpha, float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "mv3d_flow_smoothness";
+    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
+    if (H < 2) return fail(MV3D_E_INVAL, "%s: H (%d) must be at least 2", fn, H);
+    if (W < 2) return fail(MV3D_E_INVAL, "%s: W (%d) must be at least 2", fn, W);
+    const int64_t total = fs_tile_count(N, H, W);
+    if (!total) return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d need 2^31 or more tiles", fn, N, H, W);
+    if (flow_ld < 2) return fail(MV3D_E_INVAL, "%s: flow_ld (%d) smaller than 2", fn, flow_ld);
+    if (guide_c < 0 || guide_c > 4) return fail(MV3D_E_INVAL, "%s: guide_c (%d) outside 0..4", fn, guide_c);
+    if (guide_c && !guide) return fail(MV3D_E_INVAL, "%s: guide_c (%d) without a guide", fn, guide_c);
+    if (guide_c && guide_ld < guide_c) return fail(MV3D_E_INVAL, "%s: guide_ld (%d) smaller than guide_c (%d)", fn, guide_ld, guide_c);
+    if (grad_ld < 2) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than 2", fn, grad_ld);
+    {   // the largest element index of any operand, formed in int64 by the kernel
+        int ld = flow_ld > grad_ld ? flow_ld : grad_ld;
+        if (guide_c && guide_ld > ld) ld = guide_ld;
+        if ((double)N * (double)H * (double)W * (double)ld >= 4.0e18)
+            return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d at pixel stride %d overflow the element index", fn, N, H, W, ld);
+    }
+    if (grad_accumulate != 0 && grad_accumulate != 1) return fail(MV3D_E_INVAL, "%s: grad_accumulate (%d) must be 0 or 1", fn, grad_accumulate);
+    if (!std::isfinite(eps) || !(eps > 0.f)) return fail(MV3D_E_INVAL, "%s: eps (%g) must be finite and positive", fn, (double)eps);
+    if (!std::isfinite(edge_alpha) || edge_alpha < 0.f) return fail(MV3D_E_INVAL, "%s: edge_alpha (%g) must be finite and not negative", fn, (double)edge_alpha);
+    if (!std::isfinite(weight)) return fail(MV3D_E_INVAL, "%s: weight (%g) must be finite", fn, (double)weight);
+    if (!flow) return fail(MV3D_E_INVAL, "%s: flow is null", fn);
+    if (!loss_accum && !grad) return fail(MV3D_E_INVAL, "%s: loss_accum and grad are both null", fn);
+    if (!workspace) return fail(MV3D_E_INVAL, "%s: workspace is null", fn);
+    if (((uintptr_t)flow | (guide_c ? (uintptr_t)guide : 0) | (uintptr_t)loss_accum | (uintptr_t)grad) & 3)
+        return fail(MV3D_E_INVAL, "%s: flow, guide, loss_accum or grad not 4-byte aligned", fn);
+    const size_t need = mv3d_flow_smoothness_workspace_bytes(N, H, W);
+    if (workspace_bytes < need) return fail(MV3D_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    if ((uintptr_t)workspace & 15) return fail(MV3D_E_WORKSPACE, "%s: workspace not 16-byte aligned", fn);
+
+    FsArgs p = {};
+    p.flow = (const float*)flow; p.guide = guide_c ? (const float*)guide : nullptr; p.part = (double*)workspace;
+    p.loss = (float*)loss_accum; p.grad = (float*)grad;
+    p.N = N; p.H = H; p.W = W; p.flow_ld = flow_ld; p.guide_ld = guide_ld; p.grad_ld = grad_ld;
+    p.tx = cdiv(W, FS_TW); p.ty = cdiv(H, FS_TH);
+    p.accumulate = grad_accumulate;
+    // mv3d_loss_overwrite_next(): consumed by a call that writes the loss word (kept by a recorded one); a gradient-only call
+    // is no loss entry and leaves it pending
+    p.overwrite = (loss_accum && take_loss_overwrite()) ? 1 : 0;
+    // one vector load / store per pixel where stride and address allow it
+    p.flow_vec = (flow_ld % 2 == 0 && ((uintptr_t)flow & 7) == 0) ? 1 : 0;
+    p.grad_vec = (grad && grad_ld % 2 == 0 && ((uintptr_t)grad & 7) == 0) ? 1 : 0;
+    p.guide_vec = ((guide_c == 4 && guide_ld % 4 == 0 && ((uintptr_t)guide & 15) == 0) ||
+                   (guide_c == 2 && guide_ld % 2 == 0 && ((uintptr_t)guide & 7) == 0)) ? 1 : 0;
+    // the constants of the numpy twin, each formed in double and rounded to fp32 once
+    p.weight = weight;
+    p.eps = eps;
+    p.eps2 = eps * eps;                                   // fp32 product: its correctly rounded root is eps again
+    p.alpha_c = guide_c ? (float)((double)edge_alpha / (double)guide_c) : 0.f;
+    p.zx = (double)N * (double)H * (double)(W - 1) * 2.0;
+    p.zy = (double)N * (double)(H - 1) * (double)W * 2.0;
+    p.cx = (float)((double)weight / p.zx);
+    p.cy = (float)((double)weight / p.zy);
+
+    const double px = (double)N * H * W;
+    // algorithmic bytes: the flow and the guide once, the gradient written once (and read once when it accumulates), the tile
+    // sums.  FLOPs per pixel: 2 edges x 2 channels x ~8 (difference, square, add, root, quotient, products) + the guide's
+    // 2 x (2 Cg + 3) + the combination's 12.
+    const double grad_bytes = grad ? (grad_accumulate ? 16.0 : 8.0) : 0.0;
+    const double flops = px * (32.0 + (guide_c ? 2.0 * (2.0 * guide_c + 3.0) : 0.0) + (grad ? 12.0 : 0.0));
+    const OpInfo tile_info{intern_label("flow_smooth_tile"), flops,
+                           px * (8.0 + 4.0 * guide_c + grad_bytes) + (loss_accum ? (double)total * 16.0 : 0.0)};
+    const int grid = (int)total;
+    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
+        switch (guide_c) {
+            case 0: return fs_launch_tile<0>(p, grid, s);
+            case 1: return fs_launch_tile<1>(p, grid, s);
+            case 2: return fs_launch_tile<2>(p, grid, s);
+            case 3: return fs_launch_tile<3>(p, grid, s);
+            default: return fs_launch_tile<4>(p, grid, s);
+        }
+    });
+    if (rc || !loss_accum) return rc;
+    const OpInfo final_info{intern_label("flow_smooth_final"), 0.0, (double)total * 16.0 + 8.0};
+    return dispatch(stream, final_info, [=](hipStream_t s) {
+        flow_smooth_final_kernel<<<1, FS_THREADS, 0, s>>>(p);
+        return launched("flow_smooth_final_kernel");
+    });
+}
+
+}  // extern "C"

@@ -183,17 +183,21 @@ class ScalarExpr:
     __rmul__ = __mul__
 
 
-LOSS_L1, LOSS_L2, LOSS_SSIM = 1, 2, 3
+LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH = 1, 2, 3, 4
 
 
 class LossTerm:
     """One term of the loss on the differentiated tensor a against b.  kind LOSS_L1 / LOSS_L2: the pixel losses (mv3d_pixel_loss*),
     with an optional one-channel mask and a scale on b.  kind LOSS_SSIM: 1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss);
-    no mask, no scale.  `ws` is an SSIM term's own workspace, allocated by Graph.compile()."""
+    no mask, no scale.  kind LOSS_SMOOTH: the edge-aware smoothness of the flow a (mv3d_flow_smoothness) with b the guide image or
+    None, edge parameter edge_alpha and Charbonnier eps; a is usually an INTERMEDIATE tensor whose gradient also arrives from its
+    consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  `ws` is an SSIM or smoothness term's own
+    workspace, allocated by Graph.compile()."""
 
-    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0):
+    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3):
         self.a, self.b, self.kind, self.mask, self.b_scale = a, b, kind, mask, float(b_scale)
         self.max_val = float(max_val)
+        self.edge_alpha, self.eps = float(edge_alpha), float(eps)
         self.ws = None
 
 
@@ -596,6 +600,7 @@ class Graph:
         self.plan_bwd_fused = None
         self.opt_state = None
         self.plan_fwd = self.plan_bwd = None
+        self._smooth_deferred = []      # [(weight, LossTerm)]: smoothness terms whose gradient launch goes into the reverse plans
         # the update rule (model_base: AdamOptimizer, MomentumOptimizer, GradientDescentOptimizer); slots and state follow it
         self.optimizer = 'adam'
         self.momentum, self.use_nesterov = 0.0, False
@@ -726,6 +731,7 @@ class Graph:
             if not enabled or self.loss_expr is None or n.src.requires_grad:
                 continue            # the sampled image's gradient has to exist when the source needs one
             gen = n.gen
+            # (a smoothness term sits on the flow, not on gen: it leaves the head fused and adds to the flow gradient behind it)
             uses = [(w, t) for w, t in self.loss_expr.terms if t.a is gen or t.b is gen or t.mask is gen]
             if len(uses) != 1:
                 continue
@@ -793,12 +799,23 @@ class Graph:
             return
         # A pixel loss stores its gradient, the SSIM loss can add to one: the pixel terms go first, and an SSIM term accumulates
         # when an earlier term of this step has written the gradient of the same tensor (L2 + SSIM on one prediction).
+        # A smoothness term sits on an intermediate tensor (the flow).  Where the forward plan has already stored that tensor's
+        # gradient (the fused head, mv3d_warp_resample_loss), one launch gives the value and adds the gradient.  Otherwise only the
+        # value is recorded here and the gradient launch is deferred to the reverse plan (_smooth_before / _smooth_after).
         written = set()             # gradient addresses written by the terms so far
-        terms = [wt for wt in self.loss_expr.terms if wt[1].kind != LOSS_SSIM] + [wt for wt in self.loss_expr.terms if wt[1].kind == LOSS_SSIM]
+        order = lambda k: 2 if k == LOSS_SMOOTH else 1 if k == LOSS_SSIM else 0
+        terms = sorted(self.loss_expr.terms, key=lambda wt: order(wt[1].kind))      # stable: the terms of a kind keep their order
+        self._smooth_deferred = []
         for w, term in terms:
             if id(term) in self.fused_terms:
                 continue
             a, b, m = term.a, term.b, term.mask
+            if term.kind == LOSS_SMOOTH:
+                both = with_grad and a.requires_grad and a.grad_written
+                self._smooth_launch(w, term, value=True, grad=both, accumulate=both)
+                if with_grad and a.requires_grad and not both:
+                    self._smooth_deferred.append((w, term))
+                continue
             if a.C != b.C or a.rows != b.rows:
                 raise ValueError("loss operands of different shapes")
             grad = a.grad_ptr if (with_grad and a.requires_grad) else None
@@ -814,6 +831,47 @@ class Graph:
                 written.add(grad)
                 _note_grad_written(a, False)
 
+    def _smooth_launch(self, w, term, value, grad, accumulate):
+        """One mv3d_flow_smoothness call of a LOSS_SMOOTH term: the value into the loss word and / or the gradient stored into or
+        added onto the flow's gradient buffer."""
+        a, b = term.a, term.b
+        if grad and accumulate and a.grad_masked:
+            raise NotImplementedError("flow_smoothness_loss on a tensor whose gradient buffer already holds d/d(pre-activation)")
+        n, h, wd, _ = a.shape
+        self.lib.flow_smoothness(n, h, wd, a.ptr, a.ld, b.ptr if b is not None else None, b.C if b is not None else 0,
+                                 b.ld if b is not None else 0, term.edge_alpha, term.eps, float(w),
+                                 self.loss_buf.data_ptr() if value else None, a.grad_ptr if grad else None, a.ld,
+                                 1 if (grad and accumulate) else 0, term.ws.data_ptr(), term.ws.numel(), self.stream)
+        if grad:
+            _note_grad_written(a, False)
+
+    def _smooth_before(self, n, pending):
+        """Reverse plan, in front of node n's backward: a deferred smoothness term on a tensor n produces whose gradient nobody
+        has written STORES it (the term is that tensor's only source of gradient); the producer's backward then runs from it.
+        Store or add is decided per term at its launch: of several terms on one tensor the first stores and the others add."""
+        for wt in [wt for wt in pending if wt[1].a.producer is n]:
+            self._smooth_launch(wt[0], wt[1], value=False, grad=True, accumulate=wt[1].a.grad_written)
+            pending.remove(wt)
+
+    def _smooth_after(self, pending):
+        """Reverse plan, behind a node's backward: a deferred smoothness term whose tensor has just received its gradient from
+        a consumer (the resampler's backward) ADDS its own, one fp32 addition per element, before the tensor's producer runs."""
+        for wt in [wt for wt in pending if wt[1].a.grad_written]:
+            self._smooth_launch(wt[0], wt[1], value=False, grad=True, accumulate=True)
+            pending.remove(wt)
+
+    def _backward_node(self, n, pending):
+        self._smooth_before(n, pending)
+        n.backward(self)
+        self._smooth_after(pending)
+
+    @staticmethod
+    def _smooth_all_placed(pending):
+        """End of a reverse recording: a deferred term that found no place is an error, not a silently missing gradient."""
+        if pending:
+            raise RuntimeError("flow_smoothness_loss: the reverse pass has no place for the gradient of %d term(s): no node of "
+                               "this graph produces the tensor" % len(pending))
+
     def compile(self, stream=None):
         """Record the forward (+loss, +loss gradient) and backward launch sequences."""
         self.finalize()
@@ -821,6 +879,7 @@ class Graph:
         lib = self.lib
         for t in self.tensors:
             t.grad_written = t.grad_masked = False
+        self._smooth_deferred = []
         self._bind_prepared_filters()
         self._fuse_resample_losses()
         # every SSIM term keeps its per-tile sums in a workspace of its own (not the shared scratch: the term's two launches must
@@ -830,6 +889,11 @@ class Graph:
                 nbytes = int(lib.ssim_loss_workspace_bytes(*term.a.shape))
                 if not nbytes:
                     raise ValueError("ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (term.a.shape,))
+                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            if term.kind == LOSS_SMOOTH and term.ws is None:     # likewise for a smoothness term (2 sums per tile)
+                nbytes = int(lib.flow_smoothness_workspace_bytes(*term.a.shape[:3]))
+                if not nbytes:
+                    raise ValueError("flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (term.a.shape,))
                 term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._find_fc_chains()
         self.plan_fwd = lib.plan_create()
@@ -858,8 +922,9 @@ class Graph:
             suffix = len(order)         # variables[suffix:] are complete
             cut_hi = self.flat_size
             gate = 0
+            pending = list(self._smooth_deferred)
             for n in reversed(self.nodes):
-                n.backward(self)
+                self._backward_node(n, pending)
                 if isinstance(n, LinearNode):
                     gate = lib.plan_size(self.plan_bwd)
                 for v in (getattr(n, 'w', None), getattr(n, 'b', None), getattr(n, 'm', None)):
@@ -882,6 +947,7 @@ class Graph:
                 if cut_hi - lo >= self.bucket_elems or boundary:
                     self.grad_buckets.append((lib.plan_size(self.plan_bwd), lo, cut_hi))
                     cut_hi = lo
+            self._smooth_all_placed(pending)
         finally:
             lib.plan_end()
         nbwd = lib.plan_size(self.plan_bwd)
@@ -934,9 +1000,10 @@ class Graph:
                 self._fin_pending, self._fin_vars, self._fin_done, self._fin_tables = 0, [], set(), []
             lib.plan_begin(plan)
             self._fusing = True
+            pending = list(self._smooth_deferred)
             try:
                 for n in reversed(self.nodes):
-                    n.backward(self)
+                    self._backward_node(n, pending)
                     if self._finalizing and isinstance(n, ConvNode) and n.w.has_grad:
                         # the reduction (+ optimiser) of what has piled up goes out as soon as it is worth a launch: it then runs
                         # beside the rest of the pass instead of in its tail
@@ -945,6 +1012,7 @@ class Graph:
                         if self._fin_pending >= self.finalize_chunk_bytes:
                             self._finalize_commit()
                             lib.grad_finalize_begin()
+                self._smooth_all_placed(pending)
                 for n in self._fused_nodes:         # the fused fc optimiser goes behind the whole reverse pass
                     n.record_fused_update(self)
                 if self._finalizing and self._fused_vars:

@@ -238,3 +238,130 @@ def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False
     lib.ssim_loss(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld, 1 if accumulate else 0,
                   ws.data_ptr(), nbytes, stream)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ flow smoothness
+def _smooth_scalars(edge_alpha, eps, weight):
+    """(edge_alpha, eps, weight) as the floats the C ABI takes; ValueError on what mv3d_flow_smoothness would refuse."""
+    edge_alpha, eps, weight = (float(np.float32(v)) for v in (edge_alpha, eps, weight))
+    if not math.isfinite(edge_alpha) or edge_alpha < 0:
+        raise ValueError("flow_smoothness: edge_alpha must be finite and not negative")
+    if not math.isfinite(eps) or eps <= 0:
+        raise ValueError("flow_smoothness: eps must be finite and positive")
+    if not math.isfinite(weight):
+        raise ValueError("flow_smoothness: weight must be finite")
+    return edge_alpha, eps, weight
+
+
+def _smooth_shape(shape):
+    if len(shape) != 4 or shape[3] != 2:
+        raise ValueError("flow_smoothness: flow must be [N,H,W,2], got %s" % (tuple(shape),))
+    if shape[0] < 1 or shape[1] < 2 or shape[2] < 2:
+        raise ValueError("flow_smoothness: flow %s needs N >= 1 and H, W >= 2" % (tuple(shape),))
+
+
+def _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype):
+    """The operand checks of the flow-smoothness functions: (flow, guide or None) in `dtype`, and edge_alpha, eps, weight as the
+    floats the C ABI takes."""
+    f = np.asarray(flow).astype(dtype)
+    _smooth_shape(f.shape)
+    g = None
+    if guide is not None:
+        g = np.asarray(guide).astype(dtype)
+        if g.ndim != 4 or g.shape[:3] != f.shape[:3] or not 1 <= g.shape[3] <= 4:
+            raise ValueError("flow_smoothness: guide must be [N,H,W,1..4] over the flow's %s, got %s" % (f.shape[:3], g.shape))
+    edge_alpha, eps, weight = _smooth_scalars(edge_alpha, eps, weight)
+    return f, g, edge_alpha, eps, weight
+
+
+def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.float64, weight=1.0):
+    """(loss, grad) of the edge-aware first-order smoothness of a flow [N,H,W,2]: loss = weight * S, a scalar of `dtype`, and
+    grad = d loss / d flow, [N,H,W,2] in `dtype`; every step in `dtype` arithmetic.  At float32 this states mv3d_flow_smoothness's
+    own operation order (csrc/flow_smooth.hip); only the two sums behind S (the kernel keeps them in double) and exp differ.
+
+      dx = f[:, :, 1:] - f[:, :, :-1]      wx = exp(-(edge_alpha / Cg) * sum_k |I[:, :, 1:, k] - I[:, :, :-1, k]|)   (1 without a guide)
+      dy = f[:, 1:] - f[:, :-1]            wy the same along rows
+      r = sqrt(d * d + eps * eps)          phi = r - eps (Charbonnier)          phi' = d / r
+      S = sum(wx * phi(dx)) / Zx + sum(wy * phi(dy)) / Zy,      Zx = N H (W-1) 2,  Zy = N (H-1) W 2
+      grad[i, j] = (ex[i, j-1] - ex[i, j]) * (weight / Zx) + (ey[i-1, j] - ey[i, j]) * (weight / Zy),   e = w * phi', 0 out of range
+    The guide is not differentiated.  sqrt(eps * eps) == eps, so a constant flow gives exactly (0, zeros)."""
+    dtype = np.dtype(dtype).type
+    f, g, edge_alpha, eps, weight = _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype)
+    n, h, w, _ = f.shape
+    eps_t = dtype(eps)
+    eps2 = eps_t * eps_t
+    zx, zy = float(n) * h * (w - 1) * 2.0, float(n) * (h - 1) * w * 2.0
+
+    def edges(axis):
+        lo = [slice(None)] * 4
+        hi = [slice(None)] * 4
+        lo[axis], hi[axis] = slice(None, -1), slice(1, None)
+        d = f[tuple(hi)] - f[tuple(lo)]
+        if g is None:
+            wgt = np.ones(d.shape[:3] + (1,), dtype)
+        else:
+            ad = np.abs(g[tuple(hi)] - g[tuple(lo)])
+            s = np.zeros(ad.shape[:3], dtype)
+            for k in range(ad.shape[3]):                     # channels added in index order
+                s = s + ad[..., k]
+            wgt = np.exp(-(dtype(edge_alpha / g.shape[3]) * s))[..., None].astype(dtype)
+        r = np.sqrt(d * d + eps2)
+        return wgt * (d / r), wgt * (r - eps_t)
+
+    ex, vx = edges(2)
+    ey, vy = edges(1)
+    loss = dtype(weight * (float(vx.sum(dtype=dtype)) / zx + float(vy.sum(dtype=dtype)) / zy))
+    px = np.zeros((n, h, w + 1, 2), dtype)
+    px[:, :, 1:w] = ex
+    py = np.zeros((n, h + 1, w, 2), dtype)
+    py[:, 1:h] = ey
+    grad = (px[:, :, :-1] - px[:, :, 1:]) * dtype(weight / zx) + (py[:, :-1] - py[:, 1:]) * dtype(weight / zy)
+    return loss, grad
+
+
+def _same_device(a, b):
+    """A graph Tensor names its device as the graph was given it ('cuda'), a torch tensor with its index ('cuda:0')."""
+    import torch
+    a, b = torch.device(a), torch.device(b)
+    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
+
+
+def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, grad=None, accumulate=False, stream=None):
+    """mv3d_flow_smoothness on device memory: weight * S of flow_smoothness_host, and optionally its gradient with respect to the
+    flow.  flow / guide: graph Tensors (channel views included) or torch device tensors, float32 [N,H,W,2] / [N,H,W,1..4].  grad: an
+    optional float32 device tensor of the flow's shape with one pixel stride (a channel slice of a dense tensor works); it is
+    overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's current stream of the operands'
+    device).  Returns the loss as a 0-d device tensor."""
+    import torch
+    from . import _lib
+    pf, shape, f_ld, dev = _operand(flow, 'flow')
+    _smooth_shape(shape)
+    edge_alpha, eps, weight = _smooth_scalars(edge_alpha, eps, weight)      # the twin's checks: the same ValueError for the same argument
+    dev = torch.device(dev)
+    pgd, g_c, gd_ld = None, 0, 0
+    if guide is not None:
+        pgd, shape_g, gd_ld, dev_g = _operand(guide, 'guide')
+        if shape_g[:3] != shape[:3] or not 1 <= shape_g[3] <= 4:
+            raise ValueError("flow_smoothness: guide must be [N,H,W,1..4] over the flow's %s, got shape %s" % (shape[:3], shape_g))
+        if not _same_device(dev_g, dev):
+            raise ValueError("flow_smoothness: guide on %s, flow on %s" % (dev_g, dev))
+        g_c = shape_g[3]
+    if dev.type != 'cuda':
+        raise _lib.Mv3dError("flow_smoothness runs on the GPU (operands are on %s); flow_smoothness_host is the numpy form" % dev)
+    n, h, w, _ = shape
+    pg, g_ld = None, 2
+    if grad is not None:
+        if not torch.is_tensor(grad):
+            raise ValueError("flow_smoothness: grad must be a torch device tensor")
+        pg, shape_gr, g_ld, dev_gr = _operand(grad, 'grad')
+        if shape_gr != shape or not _same_device(dev_gr, dev):
+            raise ValueError("flow_smoothness: grad %s on %s does not match flow %s on %s" % (shape_gr, dev_gr, shape, dev))
+    out = torch.zeros((), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    nbytes = int(lib.flow_smoothness_workspace_bytes(n, h, w))
+    ws = _workspace(dev, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.flow_smoothness(n, h, w, pf, f_ld, pgd, g_c, gd_ld, float(edge_alpha), float(eps), float(weight), out.data_ptr(), pg, g_ld,
+                        1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+    return out

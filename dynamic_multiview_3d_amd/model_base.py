@@ -112,14 +112,53 @@ def ssim_weight_from_conf(conf):
     return w
 
 
+def flow_smoothness_from_conf(conf):
+    """(weight, edge_alpha, eps) of the flow-smoothness switch: conf['flow_smoothness_weight'] (0.0 when absent or None, which
+    leaves the loss and the recorded plans as they are), conf['flow_smoothness_edge'] (default 10; 0 or None = unguided: no guide
+    is read) and conf['flow_smoothness_eps'] (default 1e-3 pixels).  Raises ValueError on a value out of range, before any
+    device work."""
+    w = conf.get('flow_smoothness_weight')
+    w = 0.0 if w is None else float(w)
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("conf['flow_smoothness_weight'] must be finite and >= 0, got %r" % (conf['flow_smoothness_weight'],))
+    alpha = conf.get('flow_smoothness_edge', 10.0)
+    alpha = 0.0 if alpha is None else float(alpha)
+    if not np.isfinite(alpha) or alpha < 0:
+        raise ValueError("conf['flow_smoothness_edge'] must be finite and >= 0, got %r" % (conf['flow_smoothness_edge'],))
+    eps = conf.get('flow_smoothness_eps')
+    eps = 1e-3 if eps is None else float(eps)
+    if not np.isfinite(eps) or eps <= 0:
+        raise ValueError("conf['flow_smoothness_eps'] must be finite and > 0, got %r" % (conf['flow_smoothness_eps'],))
+    return w, alpha, eps
+
+
 class ModelBase(object):
     input_names = ()
     supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() set it
+    supports_flow_smoothness = False        # the classes whose build_loss() adds flow_smoothness_term() set it
 
     def _check_conf(self):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
         if ssim_weight_from_conf(self.conf) > 0 and not self.supports_ssim_loss:
             raise ValueError("%s does not support conf['ssim_loss_weight']" % type(self).__name__)
+        if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.supports_flow_smoothness:
+            raise ValueError("%s does not support conf['flow_smoothness_weight']" % type(self).__name__)
+
+    def flow_smoothness_term(self, flow, guide, name='flow'):
+        """conf['flow_smoothness_weight'] * flow_smoothness_loss(flow, guide, edge, eps) on one flow head, or 0 when the switch is
+        absent or 0 (the graph then records exactly what it recorded without the key).  The guide (the target view's colour
+        image: the flow is indexed by output pixel) is dropped when conf['flow_smoothness_edge'] is 0 or None.  evaluate()
+        reports the unweighted term as '<name>/smoothness'."""
+        from .tf_utils import flow_smoothness_loss
+        w, alpha, eps = flow_smoothness_from_conf(self.conf)
+        if w == 0:
+            return 0
+        if alpha == 0:
+            guide = None
+        if not hasattr(self, 'smoothness_terms'):
+            self.smoothness_terms = []          # [(name, flow, guide or None, edge_alpha, eps)]
+        self.smoothness_terms.append((name, flow, guide, alpha, eps))
+        return flow_smoothness_loss(flow, guide, alpha, eps) * w
 
     def ssim_term(self, pred, target):
         """conf['ssim_loss_weight'] * ssim_loss(pred, target, max_val) with max_val from this model's eval_pairs() entry of the
@@ -180,6 +219,8 @@ class ModelBase(object):
         On the GPU every batch appends its [N,3] metrics (mv3d_image_metrics) and its loss to device buffers and the host
         synchronises once, after the last batch.  On a CPU graph the numpy form (image_metrics_host) scores each batch.
         Only forward passes run: parameters, optimiser slots and the step counter are left as they were.
+        With conf['flow_smoothness_weight'] > 0 every flow head's unweighted smoothness S (mv3d_flow_smoothness; numpy form on a
+        CPU graph), averaged over the batches, is reported as '<head>/smoothness' ('flow/smoothness' for the single-head models).
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
         from . import metrics
         g = self.graph
@@ -192,28 +233,37 @@ class ModelBase(object):
         n = pairs[0][1].shape[0]
         have_loss = g.loss_expr is not None
         on_gpu = g.device.type == 'cuda'
+        smooth_terms = getattr(self, 'smoothness_terms', [])
         if on_gpu:
             scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
             losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
+            smooth = torch.zeros((num_batches, len(smooth_terms)), dtype=torch.float32, device=g.device)
         else:
             scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
             losses = np.zeros(num_batches, np.float64)
+            smooth = np.zeros((num_batches, len(smooth_terms)), np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
             if on_gpu:
                 for j, (_, pred, target, max_val) in enumerate(pairs):
                     metrics.image_metrics(pred, target, max_val, out=scores[i, j])
+                for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
+                    smooth[i, j].copy_(metrics.flow_smoothness(flow, guide, alpha, eps), non_blocking=True)
                 if have_loss:
                     losses[i].copy_(loss, non_blocking=True)
             else:
                 for j, (_, pred, target, max_val) in enumerate(pairs):
                     scores[i, j] = metrics.image_metrics_host(pred.numpy(), target.numpy(), max_val)
+                for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
+                    smooth[i, j] = float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None,
+                                                                      alpha, eps)[0])
                 if have_loss:
                     losses[i] = float(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses]).cpu()          # the one synchronisation
+            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1)]).cpu()          # the one synchronisation
             scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
-            losses = packed[scores.size:].numpy().astype(np.float64)
+            losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
+            smooth = packed[scores.size + num_batches:].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
         result = {}
         if have_loss:
             result['loss'] = float(losses.mean())
@@ -222,6 +272,8 @@ class ModelBase(object):
             result[name + '/l1'] = float(s[:, metrics.L1].mean())
             result[name + '/psnr'] = float(metrics.psnr(s[:, metrics.MSE], max_val).mean())
             result[name + '/ssim'] = float(s[:, metrics.SSIM].mean())
+        for j, term in enumerate(smooth_terms):
+            result[term[0] + '/smoothness'] = float(smooth[:, j].mean())
         result['images'] = num_batches * n
         return result
 

@@ -8,7 +8,7 @@ masked_image_loss.  The 13 reader tensors (multiobject_appflow.py:31-43) are fed
 'fully_conv' (the fc path reshapes to 4096) -- BASELINE config 5 is the 256x256 extrapolation.
 """
 from .tf_utils import *                     # noqa: F401,F403
-from .model_base import ModelBase, optimizer_from_conf
+from .model_base import ModelBase, optimizer_from_conf, flow_smoothness_from_conf
 
 INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3), ('image1_only0', 3),
           ('image1_only1', 3), ('image1_mask0', 1), ('image1_mask1', 1), ('depth0', 1), ('depth1', 1),
@@ -17,6 +17,8 @@ INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3)
 
 class MultiObjectAppFlow(ModelBase):
     supports_ssim_loss = True
+    supports_flow_smoothness = True
+
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
         self.batch_size = conf['batch_size']
@@ -62,6 +64,7 @@ class MultiObjectAppFlow(ModelBase):
             flow_field = deconv2d_msra(d1_0, [self.batch_size, H, H, flow_field_channels], 5, 5, 2, 2, "d0")
             warp_pts = warp_pts_layer(flow_field)
             gen = resample_layer(src_img, warp_pts)
+        self.flow_heads.append((scope, flow_field))
         return gen
 
     def decode_direct(self, input, scope, num_outputs=1):
@@ -74,6 +77,7 @@ class MultiObjectAppFlow(ModelBase):
         return gen
 
     def buildModel(self):
+        self.flow_heads = []        # [(scope, flow field)] of every decode_flow head, in construction order
         # convolutional encoder
         concat_list = []
         if 'use_color' in self.conf:
@@ -172,6 +176,8 @@ class MultiObjectAppFlow(ModelBase):
                 else:
                     colorloss += euclidean_loss(self.gen_image1_only0, self.image1_only0)
                     colorloss += euclidean_loss(self.gen_image1_only1, self.image1_only1)
+            for scope, flow in self.flow_heads:     # conf['flow_smoothness_weight']: one term per flow head, guided by the target view
+                colorloss += self.flow_smoothness_term(flow, self.image1, name=scope)
             self.loss += colorloss
 
         if 'use_depth' in self.conf:
@@ -195,6 +201,9 @@ class MultiObjectAppFlow(ModelBase):
             mask_loss += euclidean_loss(self.gen_image1_mask1, self.image1_mask1) * mask_factor
             self.loss += mask_loss
 
+        if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.flow_heads:
+            raise ValueError("conf['flow_smoothness_weight'] is set, but this configuration of %s builds no flow head "
+                             "(it needs 'use_color' with 'combination_image' or 'gen_sep_images')" % type(self).__name__)
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def eval_pairs(self):

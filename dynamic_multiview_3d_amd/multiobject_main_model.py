@@ -9,6 +9,8 @@ from .multiobject_appflow import MultiObjectAppFlow
 
 
 class Base_Prediction_Model(MultiObjectAppFlow):
+    supports_flow_smoothness = False        # every output is predicted directly: there is no flow to regularise
+
     def decode(self, input, scope, num_outpus=3):
         H = self.image_shape[0]
         with variable_scope(scope):

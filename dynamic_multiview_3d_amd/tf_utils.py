@@ -7,7 +7,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, ConvNode, LinearNode, ActNode, ViewNode,
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_SMOOTH, ConvNode, LinearNode, ActNode, ViewNode,
                     CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
@@ -119,6 +119,36 @@ def ssim_loss(input1, input2, max_val=1.0):
     if not (math.isfinite(float(max_val)) and float(max_val) > 0):
         raise ValueError("ssim_loss: max_val must be finite and positive")
     return ScalarExpr([(1.0, LossTerm(a, b, LOSS_SSIM, max_val=max_val))])
+
+
+def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
+    """Edge-aware first-order smoothness of a flow field [N,H,W,2] (mv3d_flow_smoothness; metrics.flow_smoothness_host states the
+    definition): the mean Charbonnier penalty sqrt(d^2 + eps^2) - eps of the horizontal plus that of the vertical differences,
+    each difference weighted by exp(-edge_alpha * mean_k |difference of the guide|) when a guide image [N,H,W,1..4] is given.
+    The flow must be differentiated (it is usually an intermediate tensor: its gradient from the consumer and this term's are
+    added); the guide must not be.  Masked and scaled operands are not supported."""
+    for v in (flow, guide):
+        if isinstance(v, (_Masked, _Scaled)):
+            raise NotImplementedError("flow_smoothness_loss of a masked or scaled operand")
+    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
+        raise ValueError("flow_smoothness_loss: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
+    _check_usable(flow)
+    if flow.shape[1] < 2 or flow.shape[2] < 2:
+        raise ValueError("flow_smoothness_loss: needs H, W >= 2, got %s" % (flow.shape,))
+    if not flow.requires_grad:
+        raise ValueError("flow_smoothness_loss: the flow is not differentiated (nothing to regularise)")
+    if guide is not None:
+        if not isinstance(guide, Tensor) or len(guide.shape) != 4 or tuple(guide.shape[:3]) != tuple(flow.shape[:3]) or not 1 <= guide.C <= 4:
+            raise ValueError("flow_smoothness_loss: guide must be [N,H,W,1..4] over the flow's %s, got %s"
+                             % (flow.shape[:3], getattr(guide, 'shape', guide)))
+        if guide.requires_grad:
+            raise NotImplementedError("flow_smoothness_loss: the guide is not differentiated; it must not require a gradient")
+    edge_alpha, eps = float(edge_alpha), float(eps)
+    if not (math.isfinite(edge_alpha) and edge_alpha >= 0):
+        raise ValueError("flow_smoothness_loss: edge_alpha must be finite and >= 0")
+    if not (math.isfinite(eps) and eps > 0):
+        raise ValueError("flow_smoothness_loss: eps must be finite and positive")
+    return ScalarExpr([(1.0, LossTerm(flow, guide, LOSS_SMOOTH, edge_alpha=edge_alpha, eps=eps))])
 
 
 # ------------------------------------------------------------------------------------------------ activations

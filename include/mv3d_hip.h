@@ -250,7 +250,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_flow_smoothness) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -307,6 +307,37 @@ size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C);
 int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
                    void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* ---- edge-aware flow smoothness: value and gradient with respect to the flow --------------------------------------------
+ * flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view works), H, W >= 2; guide (optional; NULL with
+ * guide_c == 0 = unguided) [N,H,W,guide_c] fp32 with pixel stride guide_ld, guide_c in 1..4.  With
+ *   dx[n,i,j,c] = f[n,i,j+1,c] - f[n,i,j,c] (j < W-1),   dy[n,i,j,c] = f[n,i+1,j,c] - f[n,i,j,c] (i < H-1),
+ *   wx[n,i,j] = exp(-(edge_alpha / guide_c) * sum_k |I[n,i,j+1,k] - I[n,i,j,k]|), wy the same along rows (both exactly 1 and
+ *   edge_alpha ignored without a guide),   phi(d) = sqrt(d^2 + eps^2) - eps,   phi'(d) = d / sqrt(d^2 + eps^2):
+ *   S = sum wx phi(dx) / (N H (W-1) 2) + sum wy phi(dy) / (N (H-1) W 2)
+ *   loss_accum[0] += weight * S, or = weight * S when mv3d_loss_overwrite_next() is pending on the calling thread (the flag is
+ *   consumed; a recorded call keeps what it saw; a call with loss_accum NULL leaves it pending).  One thread adds, in stream order.
+ *   grad[n,i,j,c] (pixel stride grad_ld >= 2) = or += weight * ((wx phi'(dx))[i,j-1] - (wx phi'(dx))[i,j]) / Zx
+ *                                                 + weight * ((wy phi'(dy))[i-1,j] - (wy phi'(dy))[i,j]) / Zy, out-of-range terms dropped:
+ *   stored when grad_accumulate == 0, one fp32 addition onto what is there when grad_accumulate == 1 (the flow's gradient from
+ *   its consumer).  The guide is not differentiated.  Channels outside the views are never written.
+ * loss_accum and grad are each optional, not both NULL: value only, gradient only (one launch), or both in one pass.
+ * Every step is fp32 without contraction in the order of metrics.py flow_smoothness_host at float32 (sqrt and division
+ * correctly rounded; only exp may differ in the last place); the two sums behind S are kept in double and reduced in a fixed
+ * order.  A constant flow gives a value of exactly 0 and a gradient of exactly 0.  Every gradient element has exactly one
+ * writer; there are no atomics; the same inputs give the same bits, run after run and under plan replay, and the value's bits
+ * do not depend on whether a gradient was asked for.  No state outside `workspace` (16-byte aligned,
+ * mv3d_flow_smoothness_workspace_bytes() bytes, 0 for a shape the entry refuses): the per-tile sums live there between the two
+ * launches (plan labels flow_smooth_tile, flow_smooth_final; the second only with loss_accum).
+ * MV3D_E_INVAL before any launch: N < 1; H or W < 2; N * ceil(H/16) * ceil(W/64) >= 2^31 or an element index that overflows;
+ * flow_ld < 2; guide_c outside 0..4, or non-zero with a NULL guide; guide_ld < guide_c; grad_ld < 2; grad_accumulate outside
+ * {0, 1}; eps not finite or <= 0; edge_alpha not finite or < 0; weight not finite; flow NULL; loss_accum and grad both NULL;
+ * workspace NULL; flow, guide, loss_accum or grad not 4-byte aligned.  MV3D_E_WORKSPACE: workspace too small or not 16-byte
+ * aligned.  On any error loss_accum and grad are left untouched and a pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_flow_smoothness_workspace_bytes(int N, int H, int W);
+int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
+                         float edge_alpha, float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
