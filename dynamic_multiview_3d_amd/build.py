@@ -1,4 +1,5 @@
 """Builds libmv3d_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+import glob
 import os
 import shutil
 import subprocess
@@ -49,7 +50,8 @@ def build(force=False, verbose=False):
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(HERE, "..", "include", "mv3d_hip.h")]
+    # every object depends on every header: coarse, and no header can be forgotten
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "mv3d_hip.h")]
     objs = []
     for src, extra in UNITS.items():
         s = os.path.join(CSRC, src)

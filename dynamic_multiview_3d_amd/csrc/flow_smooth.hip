@@ -23,8 +23,7 @@
 //
 // LDS: lanes run along the columns in every phase (consecutive float2 / float addresses), so no pitch needs padding against the
 // 64 banks.  9.5 KB flow halo + 4.75 KB per guide channel + 8.3 KB ex + 8.7 KB ey: 26.5 KB unguided, 45.5 KB with four channels.
-#include "common.h"
-#include <cmath>
+#include "image_common.h"
 
 namespace mv3d {
 namespace {
@@ -33,7 +32,7 @@ constexpr int FS_TW = 64;                          // tile width in pixels: one 
 constexpr int FS_TH = 16;                          // tile height
 constexpr int FS_HW = FS_TW + 2;                   // halo width
 constexpr int FS_HH = FS_TH + 2;                   // halo height
-constexpr int FS_THREADS = 256;
+constexpr int FS_THREADS = IMG_THREADS;
 constexpr int FS_ROWS = FS_TH / (FS_THREADS / FS_TW);      // pixel rows per thread in the last phase (4)
 
 static_assert(FS_THREADS % FS_TW == 0 && FS_TH % (FS_THREADS / FS_TW) == 0, "the last phase covers the tile without a remainder");
@@ -45,11 +44,6 @@ struct FsArgs {
     float alpha_c, eps, eps2, cx, cy, weight;
     double zx, zy;
 };
-
-__device__ __forceinline__ double fs_wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // one edge of one channel: d the difference, w the edge weight.  e = w * phi'(d); returns w * phi(d).
 __device__ __forceinline__ float fs_edge(float d, float w, float eps, float eps2, float& e) {
@@ -111,7 +105,8 @@ __global__ __launch_bounds__(FS_THREADS) void flow_smooth_tile_kernel(const FsAr
     __syncthreads();
 
     const bool want_value = p.loss != nullptr, want_grad = p.grad != nullptr;
-    double sx = 0.0, sy = 0.0;
+    double sums[2] = {0.0, 0.0};                            // over the horizontal edges, over the vertical ones
+    double &sx = sums[0], &sy = sums[1];
     // horizontal edges: halo row r + 1, between halo columns q and q + 1
     for (int i = tid; i < FS_TH * (FS_TW + 1); i += FS_THREADS) {
         const int r = i / (FS_TW + 1), q = i - r * (FS_TW + 1);
@@ -155,15 +150,11 @@ __global__ __launch_bounds__(FS_THREADS) void flow_smooth_tile_kernel(const FsAr
         if (want_grad) s_ey[i] = e;
     }
 
-    if (want_value) {
-        sx = fs_wave_sum(sx);
-        sy = fs_wave_sum(sy);
-        if ((tid & 63) == 0) { s_red[tid >> 6] = sx; s_red[FS_THREADS / 64 + (tid >> 6)] = sy; }
-    }
-    __syncthreads();
+    if (want_value) block_sum(sums, s_red, tid);            // uniform: either way one barrier, which ex / ey need as well
+    else __syncthreads();
     if (want_value && tid == 0) {
-        p.part[2 * (int64_t)blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-        p.part[2 * (int64_t)blockIdx.x + 1] = ((s_red[4] + s_red[5]) + s_red[6]) + s_red[7];
+        p.part[2 * (int64_t)blockIdx.x] = block_total(s_red, 0);
+        p.part[2 * (int64_t)blockIdx.x + 1] = block_total(s_red, 1);
     }
     if (!want_grad) return;
 
@@ -192,27 +183,14 @@ __global__ __launch_bounds__(FS_THREADS) void flow_smooth_tile_kernel(const FsAr
 }
 
 __global__ __launch_bounds__(FS_THREADS) void flow_smooth_final_kernel(const FsArgs p) {
-    __shared__ double s_red[2 * (FS_THREADS / 64)];
-    const int64_t total = (int64_t)p.N * p.tx * p.ty;
-    double sx = 0.0, sy = 0.0;
-    for (int64_t t = threadIdx.x; t < total; t += FS_THREADS) { sx += p.part[2 * t]; sy += p.part[2 * t + 1]; }
-    sx = fs_wave_sum(sx);
-    sy = fs_wave_sum(sy);
-    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = sx; s_red[FS_THREADS / 64 + (threadIdx.x >> 6)] = sy; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double tx = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-        const double ty = ((s_red[4] + s_red[5]) + s_red[6]) + s_red[7];
-        const float term = (float)((double)p.weight * (tx / p.zx + ty / p.zy));
-        p.loss[0] = p.overwrite ? term : p.loss[0] + term;
-    }
+    tile_sums_final<2>(p.part, (int64_t)p.N * p.tx * p.ty, p.loss, p.overwrite, [&](const double (&sum)[2]) {
+        return (float)((double)p.weight * (sum[0] / p.zx + sum[1] / p.zy));
+    });
 }
 
 // 0 when the shape is outside what the entry takes
 int64_t fs_tile_count(int N, int H, int W) {
-    if (N < 1 || H < 2 || W < 2) return 0;
-    const int64_t total = (int64_t)N * cdiv(H, FS_TH) * cdiv(W, FS_TW);
-    return total <= INT32_MAX ? total : 0;
+    return (H < 2 || W < 2) ? 0 : image_tile_count(N, H, W, FS_TH, FS_TW);
 }
 
 template <int GC>
@@ -229,8 +207,7 @@ using namespace mv3d;
 extern "C" {
 
 size_t mv3d_flow_smoothness_workspace_bytes(int N, int H, int W) {
-    const int64_t total = fs_tile_count(N, H, W);
-    return (size_t)cdiv64(total * 2 * (int64_t)sizeof(double), 256) * 256;
+    return tile_workspace_bytes(fs_tile_count(N, H, W), 2);
 }
 
 int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
@@ -241,7 +218,7 @@ int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, con
     if (H < 2) return fail(MV3D_E_INVAL, "%s: H (%d) must be at least 2", fn, H);
     if (W < 2) return fail(MV3D_E_INVAL, "%s: W (%d) must be at least 2", fn, W);
     const int64_t total = fs_tile_count(N, H, W);
-    if (!total) return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d need 2^31 or more tiles", fn, N, H, W);
+    if (!total) return fail_tiles(fn, N, H, W);
     if (flow_ld < 2) return fail(MV3D_E_INVAL, "%s: flow_ld (%d) smaller than 2", fn, flow_ld);
     if (guide_c < 0 || guide_c > 4) return fail(MV3D_E_INVAL, "%s: guide_c (%d) outside 0..4", fn, guide_c);
     if (guide_c && !guide) return fail(MV3D_E_INVAL, "%s: guide_c (%d) without a guide", fn, guide_c);
@@ -253,18 +230,15 @@ int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, con
         if ((double)N * (double)H * (double)W * (double)ld >= 4.0e18)
             return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d at pixel stride %d overflow the element index", fn, N, H, W, ld);
     }
-    if (grad_accumulate != 0 && grad_accumulate != 1) return fail(MV3D_E_INVAL, "%s: grad_accumulate (%d) must be 0 or 1", fn, grad_accumulate);
-    if (!std::isfinite(eps) || !(eps > 0.f)) return fail(MV3D_E_INVAL, "%s: eps (%g) must be finite and positive", fn, (double)eps);
+    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
+    if (int rc = check_finite(fn, "eps", eps, true)) return rc;
     if (!std::isfinite(edge_alpha) || edge_alpha < 0.f) return fail(MV3D_E_INVAL, "%s: edge_alpha (%g) must be finite and not negative", fn, (double)edge_alpha);
-    if (!std::isfinite(weight)) return fail(MV3D_E_INVAL, "%s: weight (%g) must be finite", fn, (double)weight);
-    if (!flow) return fail(MV3D_E_INVAL, "%s: flow is null", fn);
+    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
+    if (int rc = check_not_null(fn, {{"flow", flow}})) return rc;
     if (!loss_accum && !grad) return fail(MV3D_E_INVAL, "%s: loss_accum and grad are both null", fn);
-    if (!workspace) return fail(MV3D_E_INVAL, "%s: workspace is null", fn);
-    if (((uintptr_t)flow | (guide_c ? (uintptr_t)guide : 0) | (uintptr_t)loss_accum | (uintptr_t)grad) & 3)
-        return fail(MV3D_E_INVAL, "%s: flow, guide, loss_accum or grad not 4-byte aligned", fn);
-    const size_t need = mv3d_flow_smoothness_workspace_bytes(N, H, W);
-    if (workspace_bytes < need) return fail(MV3D_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-    if ((uintptr_t)workspace & 15) return fail(MV3D_E_WORKSPACE, "%s: workspace not 16-byte aligned", fn);
+    if (int rc = check_buffers(fn, "flow, guide, loss_accum or grad",
+                               (uintptr_t)flow | (guide_c ? (uintptr_t)guide : 0) | (uintptr_t)loss_accum | (uintptr_t)grad, workspace,
+                               workspace_bytes, tile_workspace_bytes(total, 2))) return rc;
 
     FsArgs p = {};
     p.flow = (const float*)flow; p.guide = guide_c ? (const float*)guide : nullptr; p.part = (double*)workspace;

@@ -1,5 +1,6 @@
 // SSIM as a training loss: loss = 1 - mean over images, windows and channels of the SSIM map S that mv3d_image_metrics averages
-// (metrics.hip: same 11 taps, same c1 / c2, same fp32 operation order up to S), and its gradient with respect to the prediction.
+// (metrics.hip: both take the taps, c1 / c2, the window pass and the terms of S from image_common.h), and its gradient with respect
+// to the prediction.
 //
 // Per window, with mx = F(a), my = F(b), sab = F(a b), s2 = F(a a + b b):
 //   A1 = 2 mx my + c1    B1 = mx^2 + my^2 + c1    A2 = 2 sab - 2 mx my + c2    B2 = s2 - (mx^2 + my^2) + c2    S = (A1/B1)(A2/B2)
@@ -11,8 +12,8 @@
 // side (the window is symmetric).  The three coefficients are written so that a == b gives Dm == 0 and Ds == -2 Dq exactly.
 //
 // Built with -ffp-contract=off: every step is fp32 in the order of the numpy twin (metrics.py ssim_loss_host at float32): in both
-// directions the horizontal pass runs before the vertical one and taps are added in index order.  Only the sum of S is kept in
-// double, in a fixed order.
+// directions the horizontal pass runs before the vertical one, each in the order image_common.h states.  Only the sum of S is
+// kept in double, in a fixed order.
 //
 // Two launches, no atomics, no device state outside the caller's workspace:
 //   tile    one workgroup per 32x32 PIXEL tile of one image, so that every gradient element has exactly one writer.  Per channel
@@ -27,15 +28,14 @@
 //
 // LDS: staged rows are 53 floats apart, forward horizontal rows and coefficient rows 43, transposed horizontal rows 33: odd
 // pitches, because in the horizontal passes the lanes of a wave run down the rows.  2*52*53*4 + 4*52*43*4 = 57.8 KB static.
-#include "common.h"
-#include <cmath>
+#include "image_common.h"
 
 namespace mv3d {
 namespace {
 
-constexpr int SL_TAPS = 11;
+constexpr int SL_TAPS = IMG_TAPS;
 constexpr int SL_PAD = SL_TAPS - 1;                // 10
-constexpr int SL_TILE = 32;                        // pixels per tile side
+constexpr int SL_TILE = IMG_TILE;                  // pixels per tile side
 constexpr int SL_WIN = SL_TILE + SL_PAD;           // 42 windows per side touch a tile
 constexpr int SL_HALO = SL_WIN + SL_PAD;           // 52 pixels per side feed them
 constexpr int SL_APITCH = SL_HALO + 1;             // 53
@@ -43,8 +43,7 @@ constexpr int SL_HPITCH = SL_WIN + 1;              // 43
 constexpr int SL_TPITCH = SL_TILE + 1;             // 33
 constexpr int SL_HG = 3;                           // forward horizontal pass: columns per item (42 = 14 * 3)
 constexpr int SL_VR = 7;                           // forward vertical pass: rows per item (42 = 6 * 7; 42 * 6 = 252 items, one round)
-constexpr int SL_THREADS = 256;
-constexpr int SL_MAX_SIDE = 32768;
+constexpr int SL_THREADS = IMG_THREADS;
 
 static_assert(SL_WIN % SL_HG == 0 && SL_WIN % SL_VR == 0, "the forward passes cover the 42 windows without a remainder");
 static_assert(SL_WIN * (SL_WIN / SL_VR) <= SL_THREADS, "one vertical item per thread");
@@ -58,11 +57,6 @@ struct SlArgs {
     float c1, c2, gscale, weight;
     float w[SL_TAPS];
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs p) {
     __shared__ float s_ab[2 * SL_HALO * SL_APITCH];        // a, b staged; later the transposed horizontal results
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
     const int64_t img = (int64_t)n * p.H * p.W;
     const int px = tid & 31, py = (tid >> 5) * 4;          // this thread's 4 pixels: rows py .. py+3 of column px
     const int wx = tid % SL_WIN, wy = (tid / SL_WIN) * SL_VR;      // its 7 windows: rows wy .. wy+6 of column wx (tid < 252)
-    double ssim = 0.0;
+    double ssim[1] = {0.0};
 
     for (int c = 0; c < p.C; ++c) {
         for (int i = tid; i < SL_HALO * SL_HALO; i += SL_THREADS) {
@@ -105,23 +99,8 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
             const int cg = i / SL_HALO, r = i - cg * SL_HALO;
             const float* ra = s_a + r * SL_APITCH + cg * SL_HG;
             const float* rb = s_b + r * SL_APITCH + cg * SL_HG;
-            float acc[4][SL_HG] = {};
-#pragma unroll
-            for (int j = 0; j < SL_HG + SL_PAD; ++j) {
-                const float va = ra[j], vb = rb[j];
-                const float ab = va * vb, ss = va * va + vb * vb;
-#pragma unroll
-                for (int o = 0; o < SL_HG; ++o) {
-                    const int k = j - o;
-                    if (k >= 0 && k < SL_TAPS) {
-                        const float wk = p.w[k];
-                        acc[0][o] = acc[0][o] + wk * va;
-                        acc[1][o] = acc[1][o] + wk * vb;
-                        acc[2][o] = acc[2][o] + wk * ab;
-                        acc[3][o] = acc[3][o] + wk * ss;
-                    }
-                }
-            }
+            float acc[4][SL_HG];
+            window_pass(p.w, acc, [&](int j, float (&v)[4]) { ssim_operands(ra[j], rb[j], v); });
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -131,39 +110,25 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
         // forward vertical pass: 7 rows of one window column per lane, then S and the three coefficients
         float dm[SL_VR], ds[SL_VR], dq[SL_VR];
         if (tid < SL_WIN * (SL_WIN / SL_VR)) {
-            float acc[4][SL_VR] = {};
-#pragma unroll
-            for (int j = 0; j < SL_VR + SL_PAD; ++j) {
-                float v[4];
+            float acc[4][SL_VR];
+            window_pass(p.w, acc, [&](int j, float (&v)[4]) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = s_h[q * SL_HALO * SL_HPITCH + (wy + j) * SL_HPITCH + wx];
-#pragma unroll
-                for (int o = 0; o < SL_VR; ++o) {
-                    const int k = j - o;
-                    if (k >= 0 && k < SL_TAPS) {
-                        const float wk = p.w[k];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[q][o] = acc[q][o] + wk * v[q];
-                    }
-                }
-            }
+            });
             const int ox = x0 - SL_PAD + wx;                              // window origin, image coordinates
 #pragma unroll
             for (int o = 0; o < SL_VR; ++o) {
                 const int oy = y0 - SL_PAD + wy + o;
                 dm[o] = ds[o] = dq[o] = 0.f;
                 if (oy >= 0 && oy < Hv && ox >= 0 && ox < Wv) {
-                    const float mx = acc[0][o], my = acc[1][o], sab = acc[2][o], s2 = acc[3][o];
-                    const float num0 = (mx * my) * 2.0f, den0 = mx * mx + my * my;
-                    const float A1 = num0 + p.c1, B1 = den0 + p.c1;
-                    const float A2 = (sab * 2.0f - num0) + p.c2, B2 = (s2 - den0) + p.c2;
-                    const float lum = A1 / B1;
-                    const float cs = A2 / B2;
-                    const float S = lum * cs;
-                    dm[o] = ((my * (A2 - A1) - (mx * S) * (B2 - B1)) * 2.0f) / (B1 * B2);
-                    ds[o] = (lum / B2) * 2.0f;
-                    dq[o] = -(S / B2);
-                    if (oy >= y0 && ox >= x0) ssim += (double)S;           // origin in the tile's own 32x32: counted here and only here
+                    const float mx = acc[0][o], my = acc[1][o];
+                    const SsimTerms t = ssim_terms(mx, my, acc[2][o], acc[3][o], p.c1, p.c2);
+                    const float lum = t.A1 / t.B1;
+                    const float S = lum * (t.A2 / t.B2);
+                    dm[o] = ((my * (t.A2 - t.A1) - (mx * S) * (t.B2 - t.B1)) * 2.0f) / (t.B1 * t.B2);
+                    ds[o] = (lum / t.B2) * 2.0f;
+                    dq[o] = -(S / t.B2);
+                    if (oy >= y0 && ox >= x0) ssim[0] += (double)S;        // origin in the tile's own 32x32: counted here and only here
                 }
             }
         }
@@ -184,22 +149,11 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
         float* const s_t = s_ab;
         for (int i = tid; i < SL_WIN * (SL_TILE / 4); i += SL_THREADS) {
             const int cg = i / SL_WIN, r = i - cg * SL_WIN;
-            float acc[3][4] = {};
-#pragma unroll
-            for (int j = 0; j < 4 + SL_PAD; ++j) {
-                float v[3];
+            float acc[3][4];
+            window_pass(p.w, acc, [&](int j, float (&v)[3]) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) v[q] = s_c[q * SL_WIN * SL_HPITCH + r * SL_HPITCH + cg * 4 + j];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    const int k = j - o;
-                    if (k >= 0 && k < SL_TAPS) {
-                        const float wk = p.w[k];
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) acc[q][o] = acc[q][o] + wk * v[q];
-                    }
-                }
-            }
+            });
 #pragma unroll
             for (int q = 0; q < 3; ++q)
 #pragma unroll
@@ -208,22 +162,11 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
         __syncthreads();
         // transposed vertical pass: 4 rows of one pixel column per lane, then the combination at the pixel
         {
-            float acc[3][4] = {};
-#pragma unroll
-            for (int j = 0; j < 4 + SL_PAD; ++j) {
-                float v[3];
+            float acc[3][4];
+            window_pass(p.w, acc, [&](int j, float (&v)[3]) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) v[q] = s_t[q * SL_WIN * SL_TPITCH + (py + j) * SL_TPITCH + px];
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    const int k = j - o;
-                    if (k >= 0 && k < SL_TAPS) {
-                        const float wk = p.w[k];
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) acc[q][o] = acc[q][o] + wk * v[q];
-                    }
-                }
-            }
+            });
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 const int y = y0 + py + o, x = x0 + px;
@@ -237,33 +180,15 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
         __syncthreads();                                                   // the staging of the next channel overwrites s_t
     }
 
-    ssim = wave_sum(ssim);
-    if ((tid & 63) == 0) s_red[tid >> 6] = ssim;
-    __syncthreads();
-    if (tid == 0) p.part[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    block_sum(ssim, s_red, tid);
+    if (tid == 0) p.part[blockIdx.x] = block_total(s_red, 0);
 }
 
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_final_kernel(const SlArgs p) {
-    __shared__ double s_red[SL_THREADS / 64];
-    const int64_t total = (int64_t)p.N * p.tx * p.ty;
-    double s = 0.0;
-    for (int64_t t = threadIdx.x; t < total; t += SL_THREADS) s += p.part[t];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double sum = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    tile_sums_final<1>(p.part, (int64_t)p.N * p.tx * p.ty, p.loss, p.overwrite, [&](const double (&sum)[1]) {
         const double windows = (double)p.N * (double)(p.H - SL_PAD) * (double)(p.W - SL_PAD) * (double)p.C;
-        const float term = (float)((double)p.weight * (1.0 - sum / windows));
-        p.loss[0] = p.overwrite ? term : p.loss[0] + term;
-    }
-}
-
-// 0 when the shape is outside what the entry takes
-int64_t tile_count(int N, int H, int W, int C) {
-    if (N < 1 || H < SL_TAPS || W < SL_TAPS || C < 1 || C > 4 || H > SL_MAX_SIDE || W > SL_MAX_SIDE) return 0;
-    const int64_t total = (int64_t)N * cdiv(H, SL_TILE) * cdiv(W, SL_TILE);
-    return total <= INT32_MAX ? total : 0;
+        return (float)((double)p.weight * (1.0 - sum[0] / windows));
+    });
 }
 
 }  // namespace
@@ -274,37 +199,22 @@ using namespace mv3d;
 extern "C" {
 
 size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C) {
-    const int64_t total = tile_count(N, H, W, C);
-    return (size_t)cdiv64(total * (int64_t)sizeof(double), 256) * 256;
+    return tile_workspace_bytes(ssim_tile_count(N, H, W, C), 1);
 }
 
 int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
                    void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
                    void* stream) {
     const char* fn = "mv3d_ssim_loss";
-    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
-    if (H < SL_TAPS) return fail(MV3D_E_INVAL, "%s: H (%d) smaller than the 11-tap window", fn, H);
-    if (W < SL_TAPS) return fail(MV3D_E_INVAL, "%s: W (%d) smaller than the 11-tap window", fn, W);
-    if (C < 1 || C > 4) return fail(MV3D_E_INVAL, "%s: C (%d) outside 1..4", fn, C);
-    if (H > SL_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: H (%d) above %d", fn, H, SL_MAX_SIDE);
-    if (W > SL_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: W (%d) above %d", fn, W, SL_MAX_SIDE);
-    const int64_t total = tile_count(N, H, W, C);
-    if (!total) return fail(MV3D_E_INVAL, "%s: N (%d) images of %d x %d need 2^31 or more tiles", fn, N, H, W);
-    if (a_ld < C) return fail(MV3D_E_INVAL, "%s: a_ld (%d) smaller than C (%d)", fn, a_ld, C);
-    if (b_ld < C) return fail(MV3D_E_INVAL, "%s: b_ld (%d) smaller than C (%d)", fn, b_ld, C);
+    int64_t total;
+    if (int rc = check_image_pair(fn, N, H, W, C, a_ld, b_ld, &total)) return rc;
     if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
-    if (grad_accumulate != 0 && grad_accumulate != 1) return fail(MV3D_E_INVAL, "%s: grad_accumulate (%d) must be 0 or 1", fn, grad_accumulate);
-    if (!std::isfinite(max_val) || !(max_val > 0.f)) return fail(MV3D_E_INVAL, "%s: max_val (%g) must be finite and positive", fn, (double)max_val);
-    if (!std::isfinite(weight)) return fail(MV3D_E_INVAL, "%s: weight (%g) must be finite", fn, (double)weight);
-    if (!a) return fail(MV3D_E_INVAL, "%s: a is null", fn);
-    if (!b) return fail(MV3D_E_INVAL, "%s: b is null", fn);
-    if (!loss_accum) return fail(MV3D_E_INVAL, "%s: loss_accum is null", fn);
-    if (!workspace) return fail(MV3D_E_INVAL, "%s: workspace is null", fn);
-    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)loss_accum | (uintptr_t)grad) & 3)
-        return fail(MV3D_E_INVAL, "%s: a, b, loss_accum or grad not 4-byte aligned", fn);
-    const size_t need = mv3d_ssim_loss_workspace_bytes(N, H, W, C);
-    if (workspace_bytes < need) return fail(MV3D_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
-    if ((uintptr_t)workspace & 15) return fail(MV3D_E_WORKSPACE, "%s: workspace not 16-byte aligned", fn);
+    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
+    if (int rc = check_finite(fn, "max_val", max_val, true)) return rc;
+    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
+    if (int rc = check_not_null(fn, {{"a", a}, {"b", b}, {"loss_accum", loss_accum}})) return rc;
+    if (int rc = check_buffers(fn, "a, b, loss_accum or grad", (uintptr_t)a | (uintptr_t)b | (uintptr_t)loss_accum | (uintptr_t)grad,
+                               workspace, workspace_bytes, tile_workspace_bytes(total, 1))) return rc;
 
     SlArgs p = {};
     p.a = (const float*)a; p.b = (const float*)b; p.part = (double*)workspace; p.loss = (float*)loss_accum; p.grad = (float*)grad;
@@ -315,17 +225,7 @@ int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const vo
     p.weight = weight;
     const double windows = (double)N * (double)(H - SL_PAD) * (double)(W - SL_PAD) * (double)C;
     p.gscale = (float)(-(double)weight / windows);
-    // the constants of the numpy twin, rounded to fp32 once (as mv3d_image_metrics computes them)
-    const double k1 = 0.01 * (double)max_val, k2 = 0.03 * (double)max_val;
-    p.c1 = (float)(k1 * k1);
-    p.c2 = (float)(k2 * k2);
-    double g[SL_TAPS], sum = 0.0;
-    for (int k = 0; k < SL_TAPS; ++k) {
-        const double d = (double)(k - SL_TAPS / 2);
-        g[k] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
-        sum += g[k];
-    }
-    for (int k = 0; k < SL_TAPS; ++k) p.w[k] = (float)(g[k] / sum);
+    ssim_constants(max_val, &p.c1, &p.c2, p.w);
 
     const double elems = (double)N * H * W * C;
     // algorithmic bytes: both images once, the gradient written once (and read once when it accumulates), the tile sums written
