@@ -14,6 +14,7 @@ from .model_base import ModelBase, optimizer_from_conf
 class AppearanceFlowModel(ModelBase):
     supports_ssim_loss = True
     supports_flow_smoothness = True
+    supports_multiscale_loss = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
@@ -45,6 +46,7 @@ class AppearanceFlowModel(ModelBase):
     def build_loss(self):
         self.loss = euclidean_loss(self.gen, self.image1) + self.ssim_term(self.gen, self.image1)      # conf['ssim_loss_weight']
         self.loss = self.loss + self.flow_smoothness_term(self.flow_field, self.image1)                 # conf['flow_smoothness_weight']
+        self.loss = self.loss + self.multiscale_term(self.flow_field, self.image0, self.image1)           # conf['multiscale_loss_levels']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def eval_pairs(self):

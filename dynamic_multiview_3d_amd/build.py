@@ -26,6 +26,7 @@ UNITS = {
     "metrics.hip": ["-ffp-contract=off"],
     "ssim_loss.hip": ["-ffp-contract=off"],
     "flow_smooth.hip": ["-ffp-contract=off"],
+    "multiscale_loss.hip": ["-ffp-contract=off"],
     "comm.hip": [],                     # RCCL resolved at run time (dlsym): no link-time dependency
     "tfrecord.hip": ["-msse4.2"],       # host code only: the input thread's record reader (hardware crc32c)
 }

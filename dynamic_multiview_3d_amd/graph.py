@@ -183,7 +183,8 @@ class ScalarExpr:
     __rmul__ = __mul__
 
 
-LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH = 1, 2, 3, 4
+LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE = 1, 2, 3, 4, 5
+FLOW_TERMS = (LOSS_SMOOTH, LOSS_MULTISCALE)     # terms on a flow, usually an intermediate tensor: their gradient launch can be deferred
 
 
 class LossTerm:
@@ -191,13 +192,18 @@ class LossTerm:
     with an optional one-channel mask and a scale on b.  kind LOSS_SSIM: 1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss);
     no mask, no scale.  kind LOSS_SMOOTH: the edge-aware smoothness of the flow a (mv3d_flow_smoothness) with b the guide image or
     None, edge parameter edge_alpha and Charbonnier eps; a is usually an INTERMEDIATE tensor whose gradient also arrives from its
-    consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  `ws` is an SSIM or smoothness term's own
-    workspace, allocated by Graph.compile()."""
+    consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  kind LOSS_MULTISCALE: the multi-scale
+    photometric loss (mv3d_multiscale_warp_loss) of the flow a, merged the same way, that warps the third operand `src` onto the
+    target b over `levels` pyramid levels with per-level weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2);
+    neither image is differentiated.  `ws` is an SSIM, smoothness or multi-scale term's own workspace, allocated by
+    Graph.compile(); a multi-scale term's also holds the pyramids its forward call builds and its reverse call reuses."""
 
-    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3):
+    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3, src=None, levels=0,
+                 level_weights=(), pixel_kind=LOSS_L2):
         self.a, self.b, self.kind, self.mask, self.b_scale = a, b, kind, mask, float(b_scale)
         self.max_val = float(max_val)
         self.edge_alpha, self.eps = float(edge_alpha), float(eps)
+        self.src, self.levels, self.level_weights, self.pixel_kind = src, int(levels), tuple(float(v) for v in level_weights), pixel_kind
         self.ws = None
 
 
@@ -803,14 +809,15 @@ class Graph:
         # gradient (the fused head, mv3d_warp_resample_loss), one launch gives the value and adds the gradient.  Otherwise only the
         # value is recorded here and the gradient launch is deferred to the reverse plan (_smooth_before / _smooth_after).
         written = set()             # gradient addresses written by the terms so far
-        order = lambda k: 2 if k == LOSS_SMOOTH else 1 if k == LOSS_SSIM else 0
+        # A multi-scale photometric term sits on the flow as well and is placed by the same rule, behind the smoothness terms.
+        order = lambda k: 3 if k == LOSS_MULTISCALE else 2 if k == LOSS_SMOOTH else 1 if k == LOSS_SSIM else 0
         terms = sorted(self.loss_expr.terms, key=lambda wt: order(wt[1].kind))      # stable: the terms of a kind keep their order
         self._smooth_deferred = []
         for w, term in terms:
             if id(term) in self.fused_terms:
                 continue
             a, b, m = term.a, term.b, term.mask
-            if term.kind == LOSS_SMOOTH:
+            if term.kind in FLOW_TERMS:
                 both = with_grad and a.requires_grad and a.grad_written
                 self._smooth_launch(w, term, value=True, grad=both, accumulate=both)
                 if with_grad and a.requires_grad and not both:
@@ -832,12 +839,23 @@ class Graph:
                 _note_grad_written(a, False)
 
     def _smooth_launch(self, w, term, value, grad, accumulate):
-        """One mv3d_flow_smoothness call of a LOSS_SMOOTH term: the value into the loss word and / or the gradient stored into or
-        added onto the flow's gradient buffer."""
+        """One call of a term on a flow (mv3d_flow_smoothness for LOSS_SMOOTH, mv3d_multiscale_warp_loss for LOSS_MULTISCALE): the
+        value into the loss word and / or the gradient stored into or added onto the flow's gradient buffer.  A multi-scale call
+        without the value is the reverse-pass call: the value call of this step has left the pyramids in the term's workspace."""
         a, b = term.a, term.b
         if grad and accumulate and a.grad_masked:
-            raise NotImplementedError("flow_smoothness_loss on a tensor whose gradient buffer already holds d/d(pre-activation)")
+            raise NotImplementedError("a loss term on a flow whose gradient buffer already holds d/d(pre-activation)")
         n, h, wd, _ = a.shape
+        if term.kind == LOSS_MULTISCALE:
+            s = term.src
+            weights = (C.c_float * term.levels)(*[float(w) * v for v in term.level_weights])
+            self.lib.multiscale_warp_loss(n, h, wd, s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, term.levels, weights,
+                                          term.pixel_kind, self.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None,
+                                          a.ld, 1 if (grad and accumulate) else 0, 0 if value else 1, term.ws.data_ptr(), term.ws.numel(),
+                                          self.stream)
+            if grad:
+                _note_grad_written(a, False)
+            return
         self.lib.flow_smoothness(n, h, wd, a.ptr, a.ld, b.ptr if b is not None else None, b.C if b is not None else 0,
                                  b.ld if b is not None else 0, term.edge_alpha, term.eps, float(w),
                                  self.loss_buf.data_ptr() if value else None, a.grad_ptr if grad else None, a.ld,
@@ -869,7 +887,7 @@ class Graph:
     def _smooth_all_placed(pending):
         """End of a reverse recording: a deferred term that found no place is an error, not a silently missing gradient."""
         if pending:
-            raise RuntimeError("flow_smoothness_loss: the reverse pass has no place for the gradient of %d term(s): no node of "
+            raise RuntimeError("a loss term on a flow: the reverse pass has no place for the gradient of %d term(s): no node of "
                                "this graph produces the tensor" % len(pending))
 
     def compile(self, stream=None):
@@ -894,6 +912,13 @@ class Graph:
                 nbytes = int(lib.flow_smoothness_workspace_bytes(*term.a.shape[:3]))
                 if not nbytes:
                     raise ValueError("flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (term.a.shape,))
+                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            if term.kind == LOSS_MULTISCALE and term.ws is None:     # the tile sums and the pyramids of src and target
+                s = term.src
+                nbytes = int(lib.multiscale_warp_loss_workspace_bytes(*term.a.shape[:3], s.shape[1], s.shape[2], s.C, term.levels))
+                if not nbytes:
+                    raise ValueError("multiscale_photometric_loss: a flow of shape %s over a source of shape %s at %d levels is outside "
+                                     "what mv3d_multiscale_warp_loss takes" % (term.a.shape, s.shape, term.levels))
                 term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._find_fc_chains()
         self.plan_fwd = lib.plan_create()

@@ -365,3 +365,157 @@ def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, gra
     lib.flow_smoothness(n, h, w, pf, f_ld, pgd, g_c, gd_ld, float(edge_alpha), float(eps), float(weight), out.data_ptr(), pg, g_ld,
                         1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ multi-scale photometric loss
+MULTISCALE_MAX_LEVELS = 3
+
+
+def _multiscale_scalars(levels, level_weights, kind):
+    """(levels, [w_l] as the floats the C ABI takes, kind); ValueError on what mv3d_multiscale_warp_loss would refuse."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= MULTISCALE_MAX_LEVELS:
+        raise ValueError("multiscale_warp_loss: levels must be an integer in 1..%d, got %r" % (MULTISCALE_MAX_LEVELS, levels))
+    levels = int(levels)
+    if level_weights is None:
+        level_weights = [1.0] * levels
+    weights = [float(np.float32(v)) for v in np.asarray(level_weights, np.float64).reshape(-1)]
+    if len(weights) != levels:
+        raise ValueError("multiscale_warp_loss: %d level_weights for %d levels" % (len(weights), levels))
+    if not all(math.isfinite(v) for v in weights):
+        raise ValueError("multiscale_warp_loss: level_weights must be finite, got %r" % (weights,))
+    if kind not in (1, 2):
+        raise ValueError("multiscale_warp_loss: kind must be 1 (absolute value) or 2 (square), got %r" % (kind,))
+    return levels, weights, int(kind)
+
+
+def _multiscale_shapes(src, flow, target, levels):
+    """Checks [N,Hs,Ws,C], [N,H,W,2], [N,H,W,C] with C in 1..4 and every side a multiple of 2^levels."""
+    src, flow, target = tuple(src), tuple(flow), tuple(target)
+    if len(flow) != 4 or flow[3] != 2:
+        raise ValueError("multiscale_warp_loss: flow must be [N,H,W,2], got %s" % (flow,))
+    if len(target) != 4 or target[:3] != flow[:3] or not 1 <= target[3] <= 4:
+        raise ValueError("multiscale_warp_loss: target must be [N,H,W,1..4] over the flow's %s, got %s" % (flow[:3], target))
+    if len(src) != 4 or src[0] != flow[0] or src[3] != target[3]:
+        raise ValueError("multiscale_warp_loss: src must be [N,Hs,Ws,C] with the target's N and C, got %s for target %s" % (src, target))
+    f = 1 << levels
+    for name, v in (('N', flow[0]), ('H', flow[1]), ('W', flow[2]), ('Hs', src[1]), ('Ws', src[2])):
+        if v < 1 or (name != 'N' and v % f):
+            raise ValueError("multiscale_warp_loss: %s (%d) must be a positive multiple of 2^levels = %d" % (name, v, 1 if name == 'N' else f))
+
+
+def _pool2(x):
+    """One pyramid step over [N,H,W,C]: 0.25 * ((p00 + p01) + (p10 + p11)) of every 2 x 2 block, in x's dtype."""
+    return x.dtype.type(0.25) * ((x[:, 0::2, 0::2] + x[:, 0::2, 1::2]) + (x[:, 1::2, 0::2] + x[:, 1::2, 1::2]))
+
+
+def _bilinear_taps(data, x, y):
+    """(valid, dx, dy, iff, icc, ifc, icf) of the sampler at (x = column, y = row) over data [N,Hs,Ws,C], in data's dtype: valid iff
+    -1 < x < Ws and -1 < y < Hs; dx = (floor(x) + 1) - x; a tap outside the image, and every tap of an invalid point, is 0.  The
+    expressions of mv3d_warp_resample_fwd / _bwd."""
+    n, hs, ws, _ = data.shape
+    one = data.dtype.type(1)
+    valid = (x > -1) & (y > -1) & (x < ws) & (y < hs)
+    fxf, fyf = np.floor(x), np.floor(y)
+    dx, dy = ((fxf + one) - x)[..., None], ((fyf + one) - y)[..., None]
+    fx = np.clip(fxf, -2, ws).astype(np.int64)          # the clip keeps the conversion defined for far-away points (not valid)
+    fy = np.clip(fyf, -2, hs).astype(np.int64)
+    b = np.broadcast_to(np.arange(n).reshape(n, 1, 1), x.shape)
+
+    def tap(yy, xx):
+        ok = valid & (xx >= 0) & (xx < ws) & (yy >= 0) & (yy < hs)
+        return np.where(ok[..., None], data[b, np.clip(yy, 0, hs - 1), np.clip(xx, 0, ws - 1)], data.dtype.type(0))
+    return valid, dx, dy, tap(fy, fx), tap(fy + 1, fx + 1), tap(fy + 1, fx), tap(fy, fx + 1)
+
+
+def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kind=2, dtype=np.float64):
+    """(value, grad, level_values) of the multi-scale photometric loss of a flow [N,H,W,2] that warps src [N,Hs,Ws,C] onto target
+    [N,H,W,C]: value = sum_l w_l T_l, a scalar of `dtype`; grad = d value / d flow, [N,H,W,2]; level_values = [T_1 .. T_L], the
+    unweighted terms; every step in `dtype` arithmetic.  At float32 this states mv3d_multiscale_warp_loss's own operation order
+    (csrc/multiscale_loss.hip); only the sums behind T_l differ (the kernel keeps them in double).  For level l = 1..L, f = 2^l:
+
+      pool_l   halves level l-1 (level 0 = the input): 0.25 * ((p00 + p01) + (p10 + p11)) of the 2 x 2 block p00 p01 / p10 p11
+               (row-major); applied to src, to target and to both channels of the flow
+      flow_l = pool_l(flow) * (1 / f);   x = flow_l[..., 0] + I (the ROW index),  y = flow_l[..., 1] + J: the sampler reads x as
+               the column and y as the row (the transposed convention of warp_pts_layer + resample_layer).  Pooling with aligned
+               pixel centres maps x to (x - (f-1)/2) / f, so the block mean is the coarse flow and no other offset appears
+      gen_l  = ((dx dy iff + (1-dx)(1-dy) icc) + dx (1-dy) ifc) + (1-dx) dy icf over pool_l(src), 0 where the point is not valid
+      d = gen_l - pool_l(target);   T_l = mean over (n,I,J) of sum_c phi(d),  phi = d d (kind 2) or |d| (kind 1)
+      s_l = w_l k / (N H_l W_l) / f^3  (k = 2 or 1), formed in double and rounded once;  g = d s_l (kind 2) or sign(d) s_l (kind 1)
+      G_l[..., 0] = sum_c g (dy (icf - iff) + (1-dy) (icc - ifc)),  G_l[..., 1] = sum_c g (dx (ifc - iff) + (1-dx) (icc - icf)),
+               channels added in index order, 0 where the point is not valid
+      grad[n,i,j] = (G_1[n, i>>1, j>>1] + G_2[n, i>>2, j>>2]) + G_3[n, i>>3, j>>3]      (1 / f^2 from the mean, 1 / f from the scaling)
+    src and target are not differentiated.  gen_l == pool_l(target) at every level gives exactly (0, zeros, zeros)."""
+    dtype = np.dtype(dtype).type
+    levels, weights, kind = _multiscale_scalars(levels, level_weights, kind)
+    s, fl, t = (np.asarray(v).astype(dtype) for v in (src, flow, target))
+    _multiscale_shapes(s.shape, fl.shape, t.shape, levels)
+    n, h, w, _ = fl.shape
+    one, zero = dtype(1), dtype(0)
+    value, grad, level_values = 0.0, None, []
+    for l in range(1, levels + 1):
+        f = 1 << l
+        s, fl, t = _pool2(s), _pool2(fl), _pool2(t)
+        hl, wl = h >> l, w >> l
+        ii, jj = np.meshgrid(np.arange(hl, dtype=dtype), np.arange(wl, dtype=dtype), indexing='ij')
+        x = fl[..., 0] * dtype(1.0 / f) + ii[None]
+        y = fl[..., 1] * dtype(1.0 / f) + jj[None]
+        valid, dx, dy, iff, icc, ifc, icf = _bilinear_taps(s, x, y)
+        gen = np.where(valid[..., None], ((dx * dy * iff + (one - dx) * (one - dy) * icc) + dx * (one - dy) * ifc) + (one - dx) * dy * icf, zero)
+        d = gen - t
+        count = float(n) * hl * wl
+        scale = dtype(weights[l - 1] * (2.0 if kind == 2 else 1.0) / count / float(f * f * f))
+        phi, g = (d * d, d * scale) if kind == 2 else (np.abs(d), np.sign(d) * scale)
+        T = dtype(float(phi.sum(dtype=dtype)) / count)
+        level_values.append(T)
+        value += weights[l - 1] * float(T)
+        tx = g * (dy * (icf - iff) + (one - dy) * (icc - ifc))
+        ty = g * (dx * (ifc - iff) + (one - dx) * (icc - icf))
+        G = np.zeros((n, hl, wl, 2), dtype)
+        for c in range(d.shape[3]):                          # channels added in index order
+            G[..., 0] = G[..., 0] + tx[..., c]
+            G[..., 1] = G[..., 1] + ty[..., c]
+        G = np.where(valid[..., None], G, zero)
+        G = np.repeat(np.repeat(G, f, axis=1), f, axis=2)
+        grad = G if grad is None else grad + G
+    return dtype(value), grad, np.array(level_values, dtype)
+
+
+def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, grad=None, accumulate=False, stream=None):
+    """mv3d_multiscale_warp_loss on device memory: the value of multiscale_warp_loss_host and the unweighted T_l, and optionally
+    the gradient with respect to the flow.  src / flow / target: graph Tensors (channel views included) or torch device tensors,
+    float32 [N,Hs,Ws,C] / [N,H,W,2] / [N,H,W,C].  grad: an optional float32 device tensor of the flow's shape with one pixel stride
+    (a channel slice of a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream`
+    (default: torch's current stream of the operands' device).  Returns (value, level_values): a 0-d and a [levels] device tensor.
+    Raises ValueError on what the C entry would refuse."""
+    import ctypes
+    import torch
+    from . import _lib
+    levels, weights, kind = _multiscale_scalars(levels, level_weights, kind)       # the twin's checks: the same ValueError
+    pf, shape, f_ld, dev = _operand(flow, 'flow')
+    ps, shape_s, s_ld, dev_s = _operand(src, 'src')
+    pt, shape_t, t_ld, dev_t = _operand(target, 'target')
+    _multiscale_shapes(shape_s, shape, shape_t, levels)
+    if not _same_device(dev_s, dev) or not _same_device(dev_t, dev):
+        raise ValueError("multiscale_warp_loss: src on %s, target on %s, flow on %s" % (dev_s, dev_t, dev))
+    dev = torch.device(dev)
+    if dev.type != 'cuda':
+        raise _lib.Mv3dError("multiscale_warp_loss runs on the GPU (operands are on %s); multiscale_warp_loss_host is the numpy form" % dev)
+    n, h, w, _ = shape
+    pg, g_ld = None, 2
+    if grad is not None:
+        if not torch.is_tensor(grad):
+            raise ValueError("multiscale_warp_loss: grad must be a torch device tensor")
+        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
+        if shape_g != shape or not _same_device(dev_g, dev):
+            raise ValueError("multiscale_warp_loss: grad %s on %s does not match flow %s on %s" % (shape_g, dev_g, shape, dev))
+    out = torch.zeros((), dtype=torch.float32, device=dev)
+    level_values = torch.zeros((levels,), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    nbytes = int(lib.multiscale_warp_loss_workspace_bytes(n, h, w, shape_s[1], shape_s[2], shape_t[3], levels))
+    ws = _workspace(dev, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.multiscale_warp_loss(n, h, w, shape_s[1], shape_s[2], shape_t[3], ps, s_ld, pf, f_ld, pt, t_ld, levels,
+                             (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
+                             1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)
+    return out, level_values

@@ -132,10 +132,41 @@ def flow_smoothness_from_conf(conf):
     return w, alpha, eps
 
 
+def multiscale_loss_from_conf(conf):
+    """(levels, [w_1 .. w_levels], kind) of the multi-scale photometric switch: conf['multiscale_loss_levels'] (1..3; absent, None
+    or 0 = off), conf['multiscale_loss_weight'] (a scalar applied to every level or a list of one weight per level, default 1.0)
+    and conf['multiscale_loss_kind'] ('l2', the default, or 'l1').  levels is 0 when the switch is off or every weight is 0, which
+    leaves the loss and the recorded plans as they are.  Raises ValueError on a value out of range, before any device work."""
+    levels = conf.get('multiscale_loss_levels')
+    if levels is None or (not isinstance(levels, bool) and levels == 0):
+        return 0, [], 'l2'
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= 3:
+        raise ValueError("conf['multiscale_loss_levels'] must be an integer in 1..3 (or 0 / None for off), got %r" % (levels,))
+    levels = int(levels)
+    w = conf.get('multiscale_loss_weight')
+    w = 1.0 if w is None else w
+    if isinstance(w, (list, tuple, np.ndarray)):
+        weights = [float(v) for v in w]
+        if len(weights) != levels:
+            raise ValueError("conf['multiscale_loss_weight'] lists %d weights for %d levels" % (len(weights), levels))
+    else:
+        weights = [float(w)] * levels
+    if not all(np.isfinite(v) and v >= 0 for v in weights):
+        raise ValueError("conf['multiscale_loss_weight'] must be finite and >= 0, got %r" % (conf['multiscale_loss_weight'],))
+    kind = conf.get('multiscale_loss_kind')
+    kind = 'l2' if kind is None else kind
+    if kind not in ('l1', 'l2'):
+        raise ValueError("conf['multiscale_loss_kind'] must be 'l2' or 'l1', got %r" % (kind,))
+    if not any(weights):
+        return 0, [], kind
+    return levels, weights, kind
+
+
 class ModelBase(object):
     input_names = ()
     supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() set it
     supports_flow_smoothness = False        # the classes whose build_loss() adds flow_smoothness_term() set it
+    supports_multiscale_loss = False        # the classes whose build_loss() adds multiscale_term() set it
 
     def _check_conf(self):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
@@ -143,6 +174,22 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['ssim_loss_weight']" % type(self).__name__)
         if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.supports_flow_smoothness:
             raise ValueError("%s does not support conf['flow_smoothness_weight']" % type(self).__name__)
+        if multiscale_loss_from_conf(self.conf)[0] > 0 and not self.supports_multiscale_loss:
+            raise ValueError("%s has no flow: it does not support conf['multiscale_loss_levels']" % type(self).__name__)
+
+    def multiscale_term(self, flow, src, target, name='flow'):
+        """multiscale_photometric_loss(flow, src, target) with the levels, weights and kind of conf['multiscale_loss_*'] on one flow
+        head, or 0 when the switch is off (the graph then records exactly what it recorded without the keys).  Raises ValueError
+        for an image size that is no multiple of 2^levels.  evaluate() reports the unweighted level terms as '<name>/photo_x2',
+        '<name>/photo_x4', '<name>/photo_x8'."""
+        from .tf_utils import multiscale_photometric_loss
+        levels, weights, kind = multiscale_loss_from_conf(self.conf)
+        if levels == 0:
+            return 0
+        if not hasattr(self, 'multiscale_terms'):
+            self.multiscale_terms = []          # [(name, flow, src, target, levels, kind)]
+        self.multiscale_terms.append((name, flow, src, target, levels, kind))
+        return multiscale_photometric_loss(flow, src, target, levels, weights, kind)
 
     def flow_smoothness_term(self, flow, guide, name='flow'):
         """conf['flow_smoothness_weight'] * flow_smoothness_loss(flow, guide, edge, eps) on one flow head, or 0 when the switch is
@@ -221,6 +268,9 @@ class ModelBase(object):
         Only forward passes run: parameters, optimiser slots and the step counter are left as they were.
         With conf['flow_smoothness_weight'] > 0 every flow head's unweighted smoothness S (mv3d_flow_smoothness; numpy form on a
         CPU graph), averaged over the batches, is reported as '<head>/smoothness' ('flow/smoothness' for the single-head models).
+        With conf['multiscale_loss_levels'] on, every flow head's unweighted level terms T_l (the level_values of
+        mv3d_multiscale_warp_loss; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/photo_x2',
+        '<head>/photo_x4' and '<head>/photo_x8'.
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
         from . import metrics
         g = self.graph
@@ -234,14 +284,18 @@ class ModelBase(object):
         have_loss = g.loss_expr is not None
         on_gpu = g.device.type == 'cuda'
         smooth_terms = getattr(self, 'smoothness_terms', [])
+        ms_terms = getattr(self, 'multiscale_terms', [])
+        ms_kind = {'l1': 1, 'l2': 2}
         if on_gpu:
             scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
             losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
             smooth = torch.zeros((num_batches, len(smooth_terms)), dtype=torch.float32, device=g.device)
+            photo = torch.zeros((num_batches, len(ms_terms), 3), dtype=torch.float32, device=g.device)
         else:
             scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
             losses = np.zeros(num_batches, np.float64)
             smooth = np.zeros((num_batches, len(smooth_terms)), np.float64)
+            photo = np.zeros((num_batches, len(ms_terms), 3), np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
             if on_gpu:
@@ -249,6 +303,8 @@ class ModelBase(object):
                     metrics.image_metrics(pred, target, max_val, out=scores[i, j])
                 for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
                     smooth[i, j].copy_(metrics.flow_smoothness(flow, guide, alpha, eps), non_blocking=True)
+                for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
+                    photo[i, j, :levels].copy_(metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1], non_blocking=True)
                 if have_loss:
                     losses[i].copy_(loss, non_blocking=True)
             else:
@@ -257,13 +313,18 @@ class ModelBase(object):
                 for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
                     smooth[i, j] = float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None,
                                                                       alpha, eps)[0])
+                for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
+                    photo[i, j, :levels] = metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None,
+                                                                             ms_kind[kind])[2]
                 if have_loss:
                     losses[i] = float(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1)]).cpu()          # the one synchronisation
+            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1)]).cpu()          # the one synchronisation
             scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
             losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
-            smooth = packed[scores.size + num_batches:].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
+            at = scores.size + num_batches
+            smooth = packed[at:at + smooth.numel()].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
+            photo = packed[at + smooth.size:].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
         result = {}
         if have_loss:
             result['loss'] = float(losses.mean())
@@ -274,6 +335,9 @@ class ModelBase(object):
             result[name + '/ssim'] = float(s[:, metrics.SSIM].mean())
         for j, term in enumerate(smooth_terms):
             result[term[0] + '/smoothness'] = float(smooth[:, j].mean())
+        for j, term in enumerate(ms_terms):
+            for l in range(term[4]):
+                result['%s/photo_x%d' % (term[0], 2 << l)] = float(photo[:, j, l].mean())
         result['images'] = num_batches * n
         return result
 

@@ -8,7 +8,7 @@ masked_image_loss.  The 13 reader tensors (multiobject_appflow.py:31-43) are fed
 'fully_conv' (the fc path reshapes to 4096) -- BASELINE config 5 is the 256x256 extrapolation.
 """
 from .tf_utils import *                     # noqa: F401,F403
-from .model_base import ModelBase, optimizer_from_conf, flow_smoothness_from_conf
+from .model_base import ModelBase, optimizer_from_conf, flow_smoothness_from_conf, multiscale_loss_from_conf
 
 INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3), ('image1_only0', 3),
           ('image1_only1', 3), ('image1_mask0', 1), ('image1_mask1', 1), ('depth0', 1), ('depth1', 1),
@@ -18,6 +18,7 @@ INPUTS = (('image0', 3), ('image0_mask0', 1), ('image0_mask1', 1), ('image1', 3)
 class MultiObjectAppFlow(ModelBase):
     supports_ssim_loss = True
     supports_flow_smoothness = True
+    supports_multiscale_loss = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
@@ -178,6 +179,13 @@ class MultiObjectAppFlow(ModelBase):
                     colorloss += euclidean_loss(self.gen_image1_only1, self.image1_only1)
             for scope, flow in self.flow_heads:     # conf['flow_smoothness_weight']: one term per flow head, guided by the target view
                 colorloss += self.flow_smoothness_term(flow, self.image1, name=scope)
+            if multiscale_loss_from_conf(self.conf)[0] > 0:     # conf['multiscale_loss_levels']: one term per flow head, on the
+                if 'gen_sep_images' in self.conf and 'masked_image_loss' in self.conf:      # operands of its own colour term
+                    raise ValueError("conf['multiscale_loss_levels'] with 'masked_image_loss': there is no masked pooled loss")
+                targets = {'dec_image1': self.image1, 'dec_image1_only0': getattr(self, 'image1_only0', None),
+                           'dec_image1_only1': getattr(self, 'image1_only1', None)}
+                for scope, flow in self.flow_heads:
+                    colorloss += self.multiscale_term(flow, self.image0, targets[scope], name=scope)
             self.loss += colorloss
 
         if 'use_depth' in self.conf:
@@ -203,6 +211,9 @@ class MultiObjectAppFlow(ModelBase):
 
         if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.flow_heads:
             raise ValueError("conf['flow_smoothness_weight'] is set, but this configuration of %s builds no flow head "
+                             "(it needs 'use_color' with 'combination_image' or 'gen_sep_images')" % type(self).__name__)
+        if multiscale_loss_from_conf(self.conf)[0] > 0 and not self.flow_heads:
+            raise ValueError("conf['multiscale_loss_levels'] is set, but this configuration of %s builds no flow head "
                              "(it needs 'use_color' with 'combination_image' or 'gen_sep_images')" % type(self).__name__)
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 

@@ -10,6 +10,7 @@ from .multiobject_appflow import MultiObjectAppFlow
 
 class Base_Prediction_Model(MultiObjectAppFlow):
     supports_flow_smoothness = False        # every output is predicted directly: there is no flow to regularise
+    supports_multiscale_loss = False
 
     def decode(self, input, scope, num_outpus=3):
         H = self.image_shape[0]

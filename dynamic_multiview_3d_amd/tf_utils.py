@@ -7,7 +7,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_SMOOTH, ConvNode, LinearNode, ActNode, ViewNode,
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
                     CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
@@ -149,6 +149,33 @@ def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
     if not (math.isfinite(eps) and eps > 0):
         raise ValueError("flow_smoothness_loss: eps must be finite and positive")
     return ScalarExpr([(1.0, LossTerm(flow, guide, LOSS_SMOOTH, edge_alpha=edge_alpha, eps=eps))])
+
+
+def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=None, kind='l2'):
+    """Coarse-to-fine photometric loss of a flow field [N,H,W,2] (mv3d_multiscale_warp_loss; metrics.multiscale_warp_loss_host
+    states the definition): sum over the levels l = 1..levels of level_weights[l-1] times the euclidean_loss ('l2') or l1_loss
+    ('l1') between the 2^l-times pooled src_img, warped by the pooled and rescaled flow, and the pooled target.  level_weights: a
+    list of `levels` finite weights (default: all 1).  The flow must be differentiated (it is usually an intermediate tensor: its
+    gradient from the sampler and this term's are added); the images must not be.  Every side of src_img [N,Hs,Ws,C] and target
+    [N,H,W,C], C <= 4, must be a multiple of 2^levels.  Masked and scaled operands are not supported."""
+    from .metrics import _multiscale_scalars, _multiscale_shapes
+    for v in (flow, src_img, target):
+        if isinstance(v, (_Masked, _Scaled)):
+            raise NotImplementedError("multiscale_photometric_loss of a masked or scaled operand")
+    if kind not in ('l1', 'l2'):
+        raise ValueError("multiscale_photometric_loss: kind must be 'l2' or 'l1', got %r" % (kind,))
+    levels, weights, _ = _multiscale_scalars(levels, level_weights, 2)
+    for v, what in ((flow, 'flow'), (src_img, 'src_img'), (target, 'target')):
+        if not isinstance(v, Tensor) or len(v.shape) != 4:
+            raise ValueError("multiscale_photometric_loss: %s must be a tensor [N,H,W,C], got %s" % (what, getattr(v, 'shape', v)))
+        _check_usable(v)
+    _multiscale_shapes(src_img.shape, flow.shape, target.shape, levels)
+    if not flow.requires_grad:
+        raise ValueError("multiscale_photometric_loss: the flow is not differentiated (nothing to learn)")
+    if src_img.requires_grad or target.requires_grad:
+        raise NotImplementedError("multiscale_photometric_loss: the images are not differentiated; they must not require a gradient")
+    return ScalarExpr([(1.0, LossTerm(flow, target, LOSS_MULTISCALE, src=src_img, levels=levels, level_weights=weights,
+                                      pixel_kind=LOSS_L2 if kind == 'l2' else LOSS_L1))])
 
 
 # ------------------------------------------------------------------------------------------------ activations

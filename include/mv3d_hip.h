@@ -250,7 +250,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_flow_smoothness) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -338,6 +338,50 @@ size_t mv3d_flow_smoothness_workspace_bytes(int N, int H, int W);
 int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
                          float edge_alpha, float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- multi-scale photometric loss of a flow: value and gradient with respect to the full-resolution flow --------------------
+ * src [N,Hs,Ws,C], target [N,H,W,C], flow [N,H,W,2], all fp32 with pixel strides src_ld / target_ld / flow_ld (channel-slice
+ * views work); C in 1..4, levels L in 1..3, and H, W, Hs, Ws multiples of 2^L.  For level l = 1..L, f = 2^l:
+ *   pool_l   halves level l-1 (level 0 = the input) in fp32: 0.25 * ((p00 + p01) + (p10 + p11)) of the 2 x 2 block
+ *            p00 p01 / p10 p11 (row-major); it applies to src, to target and to both channels of the flow
+ *   flow_l = pool_l(flow) * (1 / f)                          (exact)
+ *   warp_l[n,I,J] = flow_l[n,I,J] + (I, J): channel 0 + the row index is what the sampler reads as x (column), channel 1 + the
+ *            column index as y (row), the transposed convention of mv3d_warp_resample_fwd.  Pooling by f with aligned pixel
+ *            centres maps a full-resolution coordinate x to (x - (f-1)/2) / f, so the coarse flow is exactly the block mean
+ *   gen_l  = resample(pool_l(src), warp_l), zero outside: valid iff -1 < x < Ws/f and -1 < y < Hs/f, the fp32 expressions of
+ *            mv3d_warp_resample_fwd / _bwd
+ *   T_l    = mean over (n,I,J) of sum_c phi(gen_l - pool_l(target)); phi = the square (kind 2, the coarse euclidean_loss) or the
+ *            absolute value (kind 1, the coarse l1_loss)
+ *   term   = sum_l level_weights[l-1] * T_l    (level_weights: HOST array of `levels` floats, read at the call)
+ *   loss_accum[0] += term, or = term when mv3d_loss_overwrite_next() is pending on the calling thread (the flag is consumed; a
+ *   recorded call keeps what it saw; a call with loss_accum NULL leaves it pending).  One thread adds, in stream order.
+ *   level_values (optional, device, `levels` floats; needs loss_accum) receives the unweighted T_l.
+ *   grad[n,i,j,k] (pixel stride grad_ld >= 2) = or += sum_l level_weights[l-1] * G_l[n, i >> l, j >> l, k] / f^3 with
+ *   G_l = d T_l / d warp_l the sampler's warp gradient (1 / f^2 from the block mean, 1 / f from the scaling): stored when
+ *   grad_accumulate == 0; with grad_accumulate == 1 the levels are first added in level order in fp32 and the sum is added onto
+ *   what is there with one fp32 addition.  src and target are not differentiated.  Channels outside the views are never written.
+ * loss_accum and grad are each optional, not both NULL: value only, gradient only, or both in one call.
+ * `workspace` (16-byte aligned, mv3d_multiscale_warp_loss_workspace_bytes() bytes, 0 for a shape the entry refuses) holds the
+ * per-tile sums and the pyramids of src and target; the call keeps no other state.  pyramid_ready == 1 says the workspace
+ * already holds the pyramids of these same src and target from an earlier call (the reverse-pass call of a step): the pooling
+ * launch is skipped.  Launches (plan labels): multiscale_pyramid (unless pyramid_ready), multiscale_loss_tile,
+ * multiscale_loss_final (only with loss_accum).
+ * Every step is fp32 without contraction in the order of metrics.py multiscale_warp_loss_host at float32; the per-level sums
+ * are kept in double, reduced in a fixed order, combined in level order in double and rounded once.  Every gradient element has
+ * exactly one writer; there are no atomics; the same inputs give the same bits, run after run and under plan replay, and the
+ * value's bits do not depend on whether a gradient was asked for.  gen_l == pool_l(target) at every level gives a value of
+ * exactly 0 and a gradient of exactly 0.
+ * MV3D_E_INVAL before any launch: N < 1; C outside 1..4; levels outside 1..3; H, W, Hs or Ws not a positive multiple of
+ * 2^levels, or above 32768; 2^31 or more 32 x 32 tiles, or an element index that overflows; src_ld or target_ld < C; flow_ld or
+ * grad_ld < 2; kind outside {1, 2}; grad_accumulate or pyramid_ready outside {0, 1}; src, flow, target or level_weights NULL; a
+ * level weight that is not finite; loss_accum and grad both NULL; level_values without loss_accum; workspace NULL; src, flow,
+ * target, loss_accum, level_values or grad not 4-byte aligned.  MV3D_E_WORKSPACE: workspace too small or not 16-byte aligned.
+ * On any error loss_accum, level_values and grad are left untouched and a pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_multiscale_warp_loss_workspace_bytes(int N, int H, int W, int Hs, int Ws, int C, int levels);
+int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
+                              const void* target, int target_ld, int levels, const float* level_weights, int kind, void* loss_accum,
+                              void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
