@@ -69,6 +69,7 @@ STATUS_FUNCS = {
     "mv3d_resampler_bwd": [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, _vp],
     "mv3d_image_metrics": [_i, _i, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp],
     "mv3d_ssim_loss": [_i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
+    "mv3d_census_loss": [_i, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_smoothness": [_i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_multiscale_warp_loss": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _i, _i, _i,
                                   _vp, _sz, _vp],
@@ -129,6 +130,7 @@ OTHER_FUNCS = {
     "mv3d_resampler_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mv3d_image_metrics_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_ssim_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mv3d_census_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_multiscale_warp_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "mv3d_crc32c": (C.c_uint32, [_vp, _sz]),

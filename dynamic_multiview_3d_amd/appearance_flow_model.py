@@ -45,6 +45,7 @@ class AppearanceFlowModel(ModelBase):
 
     def build_loss(self):
         self.loss = euclidean_loss(self.gen, self.image1) + self.ssim_term(self.gen, self.image1)      # conf['ssim_loss_weight']
+        self.loss = self.loss + self.census_term(self.gen, self.image1)                                  # conf['census_loss_weight']
         self.loss = self.loss + self.flow_smoothness_term(self.flow_field, self.image1)                 # conf['flow_smoothness_weight']
         self.loss = self.loss + self.multiscale_term(self.flow_field, self.image0, self.image1)           # conf['multiscale_loss_levels']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)

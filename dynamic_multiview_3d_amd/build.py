@@ -25,6 +25,7 @@ UNITS = {
     "process_image.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
     "ssim_loss.hip": ["-ffp-contract=off"],
+    "census_loss.hip": ["-ffp-contract=off"],
     "flow_smooth.hip": ["-ffp-contract=off"],
     "multiscale_loss.hip": ["-ffp-contract=off"],
     "comm.hip": [],                     # RCCL resolved at run time (dlsym): no link-time dependency

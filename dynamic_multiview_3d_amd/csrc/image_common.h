@@ -1,5 +1,5 @@
 // The SSIM window core, the fixed-order tile sums and the entry checks shared by the image kernels: metrics.hip, ssim_loss.hip
-// and flow_smooth.hip.  The device side of what ssim_window, _valid_filter, _ssim_operands and _ssim_parts are in metrics.py.
+// flow_smooth.hip and census_loss.hip (the sums and the checks).  The device side of what ssim_window, _valid_filter, _ssim_operands and _ssim_parts are in metrics.py.
 //
 // Operation order is the contract (the three units are built with -ffp-contract=off; the fp32 helpers here switch contraction off
 // themselves as well).  It is what makes the window results the float32 results of the numpy twins, and it is stated here once:
@@ -150,6 +150,24 @@ inline int check_image_pair(const char* fn, int N, int H, int W, int C, int a_ld
     if (H > IMG_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: H (%d) above %d", fn, H, IMG_MAX_SIDE);
     if (W > IMG_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: W (%d) above %d", fn, W, IMG_MAX_SIDE);
     *total = ssim_tile_count(N, H, W, C);
+    if (!*total) return fail_tiles(fn, N, H, W);
+    if (a_ld < C) return fail(MV3D_E_INVAL, "%s: a_ld (%d) smaller than C (%d)", fn, a_ld, C);
+    if (b_ld < C) return fail(MV3D_E_INVAL, "%s: b_ld (%d) smaller than C (%d)", fn, b_ld, C);
+    return MV3D_OK;
+}
+// ... of an entry over (2 radius + 1)^2 patches (census_loss.hip): the same limits with the patch side as the smallest H, W
+inline int64_t patch_tile_count(int N, int H, int W, int C, int side) {
+    if (H < side || W < side || C < 1 || C > 4 || H > IMG_MAX_SIDE || W > IMG_MAX_SIDE) return 0;
+    return image_tile_count(N, H, W, IMG_TILE, IMG_TILE);
+}
+inline int check_patch_image_pair(const char* fn, int N, int H, int W, int C, int a_ld, int b_ld, int side, int64_t* total) {
+    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
+    if (H < side) return fail(MV3D_E_INVAL, "%s: H (%d) smaller than the %d x %d patch", fn, H, side, side);
+    if (W < side) return fail(MV3D_E_INVAL, "%s: W (%d) smaller than the %d x %d patch", fn, W, side, side);
+    if (C < 1 || C > 4) return fail(MV3D_E_INVAL, "%s: C (%d) outside 1..4", fn, C);
+    if (H > IMG_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: H (%d) above %d", fn, H, IMG_MAX_SIDE);
+    if (W > IMG_MAX_SIDE) return fail(MV3D_E_INVAL, "%s: W (%d) above %d", fn, W, IMG_MAX_SIDE);
+    *total = patch_tile_count(N, H, W, C, side);
     if (!*total) return fail_tiles(fn, N, H, W);
     if (a_ld < C) return fail(MV3D_E_INVAL, "%s: a_ld (%d) smaller than C (%d)", fn, a_ld, C);
     if (b_ld < C) return fail(MV3D_E_INVAL, "%s: b_ld (%d) smaller than C (%d)", fn, b_ld, C);

@@ -183,26 +183,27 @@ class ScalarExpr:
     __rmul__ = __mul__
 
 
-LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE = 1, 2, 3, 4, 5
+LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CENSUS = 1, 2, 3, 4, 5, 6
 FLOW_TERMS = (LOSS_SMOOTH, LOSS_MULTISCALE)     # terms on a flow, usually an intermediate tensor: their gradient launch can be deferred
 
 
 class LossTerm:
     """One term of the loss on the differentiated tensor a against b.  kind LOSS_L1 / LOSS_L2: the pixel losses (mv3d_pixel_loss*),
     with an optional one-channel mask and a scale on b.  kind LOSS_SSIM: 1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss);
-    no mask, no scale.  kind LOSS_SMOOTH: the edge-aware smoothness of the flow a (mv3d_flow_smoothness) with b the guide image or
-    None, edge parameter edge_alpha and Charbonnier eps; a is usually an INTERMEDIATE tensor whose gradient also arrives from its
+    no mask, no scale.  kind LOSS_CENSUS: the soft census loss over (2 radius + 1)^2 patches at dynamic range max_val with
+    Charbonnier eps (mv3d_census_loss); no mask, no scale.  kind LOSS_SMOOTH: the edge-aware smoothness of the flow a
+    (mv3d_flow_smoothness) with b the guide image or None, edge parameter edge_alpha and Charbonnier eps; a is usually an INTERMEDIATE tensor whose gradient also arrives from its
     consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  kind LOSS_MULTISCALE: the multi-scale
     photometric loss (mv3d_multiscale_warp_loss) of the flow a, merged the same way, that warps the third operand `src` onto the
     target b over `levels` pyramid levels with per-level weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2);
-    neither image is differentiated.  `ws` is an SSIM, smoothness or multi-scale term's own workspace, allocated by
+    neither image is differentiated.  `ws` is an SSIM, census, smoothness or multi-scale term's own workspace, allocated by
     Graph.compile(); a multi-scale term's also holds the pyramids its forward call builds and its reverse call reuses."""
 
     def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3, src=None, levels=0,
-                 level_weights=(), pixel_kind=LOSS_L2):
+                 level_weights=(), pixel_kind=LOSS_L2, radius=3):
         self.a, self.b, self.kind, self.mask, self.b_scale = a, b, kind, mask, float(b_scale)
         self.max_val = float(max_val)
-        self.edge_alpha, self.eps = float(edge_alpha), float(eps)
+        self.edge_alpha, self.eps, self.radius = float(edge_alpha), float(eps), int(radius)
         self.src, self.levels, self.level_weights, self.pixel_kind = src, int(levels), tuple(float(v) for v in level_weights), pixel_kind
         self.ws = None
 
@@ -742,8 +743,8 @@ class Graph:
             if len(uses) != 1:
                 continue
             w, t = uses[0]
-            if t.kind == LOSS_SSIM:
-                continue            # the SSIM loss needs gen and writes its gradient in HBM: it never fuses
+            if t.kind in (LOSS_SSIM, LOSS_CENSUS):
+                continue            # the SSIM and census losses need gen and write their gradient in HBM: they never fuse
             if t.a is not gen or t.mask is not None or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
                 continue
             if gen.C > 4 or gen.ld != gen.C or gen.storage.has_alias or gen.storage.alias_of is not None:
@@ -803,14 +804,15 @@ class Graph:
     def _emit_losses(self, with_grad):
         if self.loss_expr is None:
             return
-        # A pixel loss stores its gradient, the SSIM loss can add to one: the pixel terms go first, and an SSIM term accumulates
-        # when an earlier term of this step has written the gradient of the same tensor (L2 + SSIM on one prediction).
+        # A pixel loss stores its gradient, the SSIM and census losses can add to one: the pixel terms go first, then the SSIM
+        # terms, then the census terms, and each of the latter accumulates when an earlier term of this step has written the
+        # gradient of the same tensor (L2 + SSIM + census on one prediction).
         # A smoothness term sits on an intermediate tensor (the flow).  Where the forward plan has already stored that tensor's
         # gradient (the fused head, mv3d_warp_resample_loss), one launch gives the value and adds the gradient.  Otherwise only the
         # value is recorded here and the gradient launch is deferred to the reverse plan (_smooth_before / _smooth_after).
         written = set()             # gradient addresses written by the terms so far
         # A multi-scale photometric term sits on the flow as well and is placed by the same rule, behind the smoothness terms.
-        order = lambda k: 3 if k == LOSS_MULTISCALE else 2 if k == LOSS_SMOOTH else 1 if k == LOSS_SSIM else 0
+        order = lambda k: {LOSS_SSIM: 1, LOSS_CENSUS: 2, LOSS_SMOOTH: 3, LOSS_MULTISCALE: 4}.get(k, 0)
         terms = sorted(self.loss_expr.terms, key=lambda wt: order(wt[1].kind))      # stable: the terms of a kind keep their order
         self._smooth_deferred = []
         for w, term in terms:
@@ -830,6 +832,11 @@ class Graph:
                 n, h, wd, c = a.shape
                 self.lib.ssim_loss(n, h, wd, c, a.ptr, a.ld, b.ptr, b.ld, term.max_val, float(w), self.loss_buf.data_ptr(), grad, a.ld,
                                    1 if grad in written else 0, term.ws.data_ptr(), term.ws.numel(), self.stream)
+            elif term.kind == LOSS_CENSUS:
+                n, h, wd, c = a.shape
+                self.lib.census_loss(n, h, wd, c, a.ptr, a.ld, b.ptr, b.ld, term.radius, term.max_val, term.eps, float(w),
+                                     self.loss_buf.data_ptr(), grad, a.ld, 1 if grad in written else 0, term.ws.data_ptr(),
+                                     term.ws.numel(), self.stream)
             else:
                 self.lib.pixel_loss_strided(a.rows, a.C, a.ptr, a.ld, b.ptr, b.ld, term.b_scale,
                                             m.ptr if m is not None else None, m.ld if m is not None else 1,
@@ -907,6 +914,12 @@ class Graph:
                 nbytes = int(lib.ssim_loss_workspace_bytes(*term.a.shape))
                 if not nbytes:
                     raise ValueError("ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (term.a.shape,))
+                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            if term.kind == LOSS_CENSUS and term.ws is None:     # likewise for a census term
+                nbytes = int(lib.census_loss_workspace_bytes(*term.a.shape, term.radius))
+                if not nbytes:
+                    raise ValueError("census_loss: operands of shape %s at radius %d are outside what mv3d_census_loss takes"
+                                     % (term.a.shape, term.radius))
                 term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             if term.kind == LOSS_SMOOTH and term.ws is None:     # likewise for a smoothness term (2 sums per tile)
                 nbytes = int(lib.flow_smoothness_workspace_bytes(*term.a.shape[:3]))

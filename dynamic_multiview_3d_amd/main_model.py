@@ -110,6 +110,7 @@ class Base_Prediction_Model(ModelBase):
         if 'use_color' in self.conf:
             self.loss += euclidean_loss(self.gen_image1, self.image1)
             self.loss += self.ssim_term(self.gen_image1, self.image1)      # conf['ssim_loss_weight']; the depth term stays L2
+            self.loss += self.census_term(self.gen_image1, self.image1)    # conf['census_loss_weight']; likewise
         if 'use_depth' in self.conf:
             self.loss += euclidean_loss(self.gen_dimage1, self.dimage1) * self.conf['depth_lr_factor']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)

@@ -519,3 +519,148 @@ def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, 
                              (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
                              1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)
     return out, level_values
+
+
+# ------------------------------------------------------------------------------------------------ census (ternary) loss
+CENSUS_MAX_RADIUS = 3
+
+
+def _census_scalars(max_val, weight, radius, eps):
+    """(max_val, weight, radius, eps) with the floats as the C ABI takes them; ValueError on what mv3d_census_loss would refuse."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= CENSUS_MAX_RADIUS:
+        raise ValueError("census_loss: radius must be an integer in 1..%d, got %r" % (CENSUS_MAX_RADIUS, radius))
+    max_val, weight, eps = (float(np.float32(v)) for v in (max_val, weight, eps))
+    if not math.isfinite(max_val) or max_val <= 0:
+        raise ValueError("census_loss: max_val must be finite and positive")
+    if not math.isfinite(eps) or eps <= 0:
+        raise ValueError("census_loss: eps must be finite and positive")
+    if not math.isfinite(weight):
+        raise ValueError("census_loss: weight must be finite")
+    return max_val, weight, int(radius), eps
+
+
+def _census_shape(shape, shape_b, radius):
+    shape, shape_b = tuple(shape), tuple(shape_b)
+    if len(shape) != 4 or shape != shape_b:
+        raise ValueError("census_loss: operands must be [N,H,W,C] of one shape, got %s and %s" % (shape, shape_b))
+    if shape[0] < 1 or not 1 <= shape[3] <= 4:
+        raise ValueError("census_loss: needs N >= 1 and C in 1..4, got %s" % (shape,))
+    side = 2 * radius + 1
+    if shape[1] < side or shape[2] < side:
+        raise ValueError("census_loss: images of %d x %d are smaller than the %d x %d patch" % (shape[1], shape[2], side, side))
+
+
+def census_offsets(radius):
+    """The K = (2r+1)^2 - 1 offsets (dy, dx) of the patch, centre excluded, row-major: dy outer, dx inner."""
+    return [(dy, dx) for dy in range(-radius, radius + 1) for dx in range(-radius, radius + 1) if (dy, dx) != (0, 0)]
+
+
+def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, eps=0.01):
+    """(loss, grad) of the soft census (ternary) loss of Meister et al. ("UnFlow") / Liu et al. ("DDFlow"): loss = weight *
+    census_loss, a scalar of `dtype`, and grad = d loss / d a, [N,H,W,C] in `dtype`; every step in `dtype` arithmetic.  At float32
+    this states mv3d_census_loss's own operation order (csrc/census_loss.hip); only the sum behind the mean differs (the kernel
+    keeps it in double).
+
+    a (prediction) and b (target) [N,H,W,C], C in 1..4; radius r in {1, 2, 3}; K = (2r+1)^2 - 1 offsets o of the (2r+1)^2 patch,
+    centre excluded, row-major (dy outer, dx inner); Hv = H - 2r, Wv = W - 2r; a pixel is valid when its whole patch is inside the
+    image.
+      g_x(p)   = (255 / max_val) (1/C) sum_c x(p,c)        intensity on the 0..255 scale: the constants mean what they mean in the
+                                                           literature
+      d_x(p,o) = g_x(p+o) - g_x(p)       R_x(p,o) = sqrt(0.81 + d_x^2)       t_x(p,o) = d_x / R_x
+      u(p,o)   = t_a - t_b               e = u^2
+      dist(p)  = (1/K) sum_o e / (0.1 + e)                 in [0, 1)
+      root(p)  = sqrt(dist + eps^2)      rho(p) = dist / (root + eps)        the Charbonnier penalty root - eps, written so that
+                                                                             dist == 0 gives exactly 0 whatever the rounding
+      census_loss = (1 / (N Hv Wv)) sum over n and the valid p of rho(p)
+    Gradient:
+      phi(p,o) = [0.1 / (0.1 + e)^2] 2 u 0.81 / R_a^3      rho'(p) = 1 / (2 root(p))
+      dL/dg_a(q) = (1 / (K N Hv Wv)) ( sum_{o : q-o valid} rho'(q-o) phi(q-o, o) - [q valid] rho'(q) sum_o phi(q, o) )
+      grad(q,c)  = weight (255 / (max_val C)) dL/dg_a(q)   the same for every channel c
+    Pixels outside the valid region still receive a gradient as neighbours.  a == b gives a loss of exactly 0 and a gradient of
+    exactly 0, because u == 0.
+
+    Order of the steps: the channels of g are added in index order and scaled by 255 / (max_val C) rounded once; dist adds its K
+    terms in offset order and multiplies by 1/K rounded once; phi = (0.162 u) / ((0.1 + e)^2 (R_a R_a R_a)); the second sum of
+    the bracket runs in offset order and the first in reverse offset order (the order in which a kernel that gathers at q meets
+    them: phi(q-o, o) == -phi(q, -o) exactly); the bracket is first - rho'(q) * second, times weight 255 / (max_val C K N Hv Wv)
+    rounded once."""
+    dtype = np.dtype(dtype).type
+    max_val, weight, r, eps = _census_scalars(max_val, weight, radius, eps)
+    a, b = np.asarray(a).astype(dtype), np.asarray(b).astype(dtype)
+    _census_shape(a.shape, b.shape, r)
+    n, h, w, c = a.shape
+    hv, wv = h - 2 * r, w - 2 * r
+    offsets = census_offsets(r)
+    k = len(offsets)
+    count = float(n) * hv * wv
+    gs = dtype(255.0 / (max_val * c))
+    c81, c01, c162, half = dtype(0.81), dtype(0.1), dtype(0.162), dtype(0.5)
+
+    def gray(x):
+        s = x[..., 0]
+        for ch in range(1, c):                               # channels added in index order
+            s = s + x[..., ch]
+        return s * gs
+
+    ga, gb = gray(a), gray(b)
+    ca, cb = ga[:, r:r + hv, r:r + wv], gb[:, r:r + hv, r:r + wv]
+    acc = np.zeros((n, hv, wv), dtype)
+    phi = []
+    for dy, dx in offsets:
+        da = ga[:, r + dy:r + dy + hv, r + dx:r + dx + wv] - ca
+        db = gb[:, r + dy:r + dy + hv, r + dx:r + dx + wv] - cb
+        ra, rb = np.sqrt(da * da + c81), np.sqrt(db * db + c81)
+        u = da / ra - db / rb
+        e = u * u
+        den = c01 + e
+        acc = acc + e / den
+        phi.append((u * c162) / ((den * den) * ((ra * ra) * ra)))
+    dist = acc * dtype(1.0 / k)
+    eps_t = dtype(eps)
+    root = np.sqrt(dist + eps_t * eps_t)
+    rho = dist / (root + eps_t)
+    loss = dtype(weight * (float(rho.sum(dtype=dtype)) / count))
+    dr = half / root
+    second = np.zeros((n, hv, wv), dtype)
+    for f in phi:
+        second = second + f
+    first = np.zeros((n, h, w), dtype)
+    for (dy, dx), f in reversed(list(zip(offsets, phi))):
+        first[:, r + dy:r + dy + hv, r + dx:r + dx + wv] = first[:, r + dy:r + dy + hv, r + dx:r + dx + wv] + dr * f
+    first[:, r:r + hv, r:r + wv] = first[:, r:r + hv, r:r + wv] - dr * second
+    grad = first * dtype(weight * 255.0 / (max_val * c) / (k * count))
+    return loss, np.ascontiguousarray(np.broadcast_to(grad[..., None], a.shape))
+
+
+def census_loss(a, b, max_val=1.0, weight=1.0, radius=3, eps=0.01, grad=None, accumulate=False, stream=None):
+    """mv3d_census_loss on device memory: weight * census_loss of a (the prediction) against b (the target), and optionally its
+    gradient with respect to a.  a / b: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with the
+    operand rules of image_metrics.  grad: an optional float32 device tensor of a's shape with one pixel stride (a channel slice of
+    a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's
+    current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
+    import torch
+    from . import _lib
+    pa, shape, a_ld, dev = _operand(a, 'pred')
+    pb, shape_b, b_ld, dev_b = _operand(b, 'target')
+    if shape != shape_b:
+        raise ValueError("census_loss: pred %s and target %s differ in shape" % (shape, shape_b))
+    dev = torch.device(dev)
+    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
+        raise _lib.Mv3dError("census_loss runs on the GPU (operands are on %s); census_loss_host is the numpy form" % dev)
+    n, h, w, c = shape
+    pg, g_ld = None, c
+    if grad is not None:
+        if not torch.is_tensor(grad):
+            raise ValueError("census_loss: grad must be a torch device tensor")
+        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
+        if shape_g != shape or torch.device(dev_g) != dev:
+            raise ValueError("census_loss: grad %s on %s does not match pred %s on %s" % (shape_g, dev_g, shape, dev))
+    out = torch.zeros((), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    nbytes = int(lib.census_loss_workspace_bytes(n, h, w, c, int(radius)))
+    ws = _workspace(dev, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.census_loss(n, h, w, c, pa, a_ld, pb, b_ld, int(radius), float(max_val), float(eps), float(weight), out.data_ptr(), pg, g_ld,
+                    1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+    return out

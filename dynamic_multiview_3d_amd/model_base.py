@@ -112,6 +112,25 @@ def ssim_weight_from_conf(conf):
     return w
 
 
+def census_from_conf(conf):
+    """(weight, radius, eps) of the census-loss switch: conf['census_loss_weight'] (0.0 when absent or None, which leaves the loss
+    and the recorded plans as they are), conf['census_loss_radius'] (default 3, an int in 1..3) and conf['census_loss_eps'] (the
+    Charbonnier epsilon, default 0.01).  Raises ValueError on a value out of range, before any device work."""
+    w = conf.get('census_loss_weight')
+    w = 0.0 if w is None else float(w)
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("conf['census_loss_weight'] must be finite and >= 0, got %r" % (conf['census_loss_weight'],))
+    radius = conf.get('census_loss_radius')
+    radius = 3 if radius is None else radius
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= 3:
+        raise ValueError("conf['census_loss_radius'] must be an integer in 1..3, got %r" % (radius,))
+    eps = conf.get('census_loss_eps')
+    eps = 0.01 if eps is None else float(eps)
+    if not np.isfinite(eps) or eps <= 0:
+        raise ValueError("conf['census_loss_eps'] must be finite and > 0, got %r" % (conf['census_loss_eps'],))
+    return w, int(radius), eps
+
+
 def flow_smoothness_from_conf(conf):
     """(weight, edge_alpha, eps) of the flow-smoothness switch: conf['flow_smoothness_weight'] (0.0 when absent or None, which
     leaves the loss and the recorded plans as they are), conf['flow_smoothness_edge'] (default 10; 0 or None = unguided: no guide
@@ -164,7 +183,7 @@ def multiscale_loss_from_conf(conf):
 
 class ModelBase(object):
     input_names = ()
-    supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() set it
+    supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() and census_term() set it
     supports_flow_smoothness = False        # the classes whose build_loss() adds flow_smoothness_term() set it
     supports_multiscale_loss = False        # the classes whose build_loss() adds multiscale_term() set it
 
@@ -172,6 +191,8 @@ class ModelBase(object):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
         if ssim_weight_from_conf(self.conf) > 0 and not self.supports_ssim_loss:
             raise ValueError("%s does not support conf['ssim_loss_weight']" % type(self).__name__)
+        if census_from_conf(self.conf)[0] > 0 and not self.supports_ssim_loss:
+            raise ValueError("%s does not support conf['census_loss_weight']" % type(self).__name__)
         if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.supports_flow_smoothness:
             raise ValueError("%s does not support conf['flow_smoothness_weight']" % type(self).__name__)
         if multiscale_loss_from_conf(self.conf)[0] > 0 and not self.supports_multiscale_loss:
@@ -218,6 +239,24 @@ class ModelBase(object):
             if p is pred and t is target:
                 return ssim_loss(pred, target, max_val) * w
         raise RuntimeError("ssim_term: eval_pairs() of %s has no entry for this pair" % type(self).__name__)
+
+    def census_term(self, pred, target):
+        """conf['census_loss_weight'] * census_loss(pred, target, max_val, radius, eps) with max_val from this model's eval_pairs()
+        entry of the pair and radius, eps from conf['census_loss_radius' / '_eps'], or 0 when the switch is absent or 0 (the graph
+        then records exactly what it recorded without the key).  Raises ValueError for an image smaller than the patch.
+        evaluate() reports the unweighted term as '<pair>/census'."""
+        from .tf_utils import census_loss
+        w, radius, eps = census_from_conf(self.conf)
+        if w == 0:
+            return 0
+        for name, p, t, max_val in self.eval_pairs():
+            if p is pred and t is target:
+                term = census_loss(pred, target, max_val, radius, eps) * w
+                if not hasattr(self, 'census_terms'):
+                    self.census_terms = []          # [(pair name, pred, target, max_val, radius, eps)]
+                self.census_terms.append((name, pred, target, max_val, radius, eps))
+                return term
+        raise RuntimeError("census_term: eval_pairs() of %s has no entry for this pair" % type(self).__name__)
 
     def _make_graph(self, device, seed):
         self._check_conf()
@@ -271,6 +310,8 @@ class ModelBase(object):
         With conf['multiscale_loss_levels'] on, every flow head's unweighted level terms T_l (the level_values of
         mv3d_multiscale_warp_loss; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/photo_x2',
         '<head>/photo_x4' and '<head>/photo_x8'.
+        With conf['census_loss_weight'] > 0 the unweighted census term of every pair that carries one (mv3d_census_loss; numpy
+        form on a CPU graph), averaged over the batches, is reported as '<pair>/census'.
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
         from . import metrics
         g = self.graph
@@ -286,16 +327,19 @@ class ModelBase(object):
         smooth_terms = getattr(self, 'smoothness_terms', [])
         ms_terms = getattr(self, 'multiscale_terms', [])
         ms_kind = {'l1': 1, 'l2': 2}
+        census_terms = getattr(self, 'census_terms', [])
         if on_gpu:
             scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
             losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
             smooth = torch.zeros((num_batches, len(smooth_terms)), dtype=torch.float32, device=g.device)
             photo = torch.zeros((num_batches, len(ms_terms), 3), dtype=torch.float32, device=g.device)
+            census = torch.zeros((num_batches, len(census_terms)), dtype=torch.float32, device=g.device)
         else:
             scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
             losses = np.zeros(num_batches, np.float64)
             smooth = np.zeros((num_batches, len(smooth_terms)), np.float64)
             photo = np.zeros((num_batches, len(ms_terms), 3), np.float64)
+            census = np.zeros((num_batches, len(census_terms)), np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
             if on_gpu:
@@ -305,6 +349,8 @@ class ModelBase(object):
                     smooth[i, j].copy_(metrics.flow_smoothness(flow, guide, alpha, eps), non_blocking=True)
                 for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
                     photo[i, j, :levels].copy_(metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1], non_blocking=True)
+                for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
+                    census[i, j].copy_(metrics.census_loss(pred, target, max_val, 1.0, radius, eps), non_blocking=True)
                 if have_loss:
                     losses[i].copy_(loss, non_blocking=True)
             else:
@@ -316,15 +362,18 @@ class ModelBase(object):
                 for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
                     photo[i, j, :levels] = metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None,
                                                                              ms_kind[kind])[2]
+                for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
+                    census[i, j] = float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0])
                 if have_loss:
                     losses[i] = float(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1)]).cpu()          # the one synchronisation
+            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1)]).cpu()          # the one synchronisation
             scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
             losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
             at = scores.size + num_batches
             smooth = packed[at:at + smooth.numel()].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
-            photo = packed[at + smooth.size:].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
+            photo = packed[at + smooth.size:at + smooth.size + photo.numel()].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
+            census = packed[at + smooth.size + photo.size:].numpy().astype(np.float64).reshape(num_batches, len(census_terms))
         result = {}
         if have_loss:
             result['loss'] = float(losses.mean())
@@ -338,6 +387,8 @@ class ModelBase(object):
         for j, term in enumerate(ms_terms):
             for l in range(term[4]):
                 result['%s/photo_x%d' % (term[0], 2 << l)] = float(photo[:, j, l].mean())
+        for j, term in enumerate(census_terms):
+            result[term[0] + '/census'] = float(census[:, j].mean())
         result['images'] = num_batches * n
         return result
 

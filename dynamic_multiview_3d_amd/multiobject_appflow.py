@@ -170,6 +170,7 @@ class MultiObjectAppFlow(ModelBase):
             if 'combination_image' in self.conf:
                 colorloss += euclidean_loss(self.gen_image1, self.image1)
                 colorloss += self.ssim_term(self.gen_image1, self.image1)      # conf['ssim_loss_weight']; every other term stays L2
+                colorloss += self.census_term(self.gen_image1, self.image1)    # conf['census_loss_weight']; likewise
             if 'gen_sep_images' in self.conf:
                 if 'masked_image_loss' in self.conf:
                     colorloss += masked_euclidean_loss(self.gen_image1_only0, self.image1_only0, self.image1_mask0)

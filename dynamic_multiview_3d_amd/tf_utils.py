@@ -7,7 +7,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_CENSUS, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
                     CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
@@ -119,6 +119,27 @@ def ssim_loss(input1, input2, max_val=1.0):
     if not (math.isfinite(float(max_val)) and float(max_val) > 0):
         raise ValueError("ssim_loss: max_val must be finite and positive")
     return ScalarExpr([(1.0, LossTerm(a, b, LOSS_SSIM, max_val=max_val))])
+
+
+def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01):
+    """The soft census (ternary) loss of the prediction against the target (mv3d_census_loss; metrics.census_loss_host states the
+    definition): the mean over images and fully-inside (2 radius + 1)^2 patches of the Charbonnier penalty (parameter eps) of the
+    distance between the two images' soft census signatures, computed on the channel mean scaled to 0..255 by max_val.  Operands
+    [N,H,W,C] with H, W >= 2 radius + 1, C <= 4 and radius in 1..3; exactly one of them is differentiated, and it goes first (the
+    value does not depend on the order, the gradient is the differentiated operand's).  Masked and scaled operands are not
+    supported."""
+    from .metrics import _census_scalars, _census_shape
+    for v in (input1, input2):
+        if isinstance(v, (_Masked, _Scaled)):
+            raise NotImplementedError("census_loss of a masked or scaled operand")
+    a, b = input1, input2
+    if b.requires_grad and not a.requires_grad:
+        a, b = b, a
+    elif a.requires_grad and b.requires_grad:
+        raise NotImplementedError("loss between two differentiated tensors")
+    max_val, _, radius, eps = _census_scalars(max_val, 1.0, radius, eps)
+    _census_shape(a.shape, b.shape, radius)
+    return ScalarExpr([(1.0, LossTerm(a, b, LOSS_CENSUS, max_val=max_val, eps=eps, radius=radius))])
 
 
 def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):

@@ -250,7 +250,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -307,6 +307,45 @@ size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C);
 int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
                    void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* ---- census (ternary) loss: value and gradient with respect to the prediction --------------------------------------------
+ * The soft census transform of Meister et al. ("UnFlow") / Liu et al. ("DDFlow").  a (prediction), b (target) [N,H,W,C] fp32 with
+ * pixel strides a_ld / b_ld (channel-slice views work), C in 1..4; radius r in {1, 2, 3}; K = (2r+1)^2 - 1 offsets o of the
+ * (2r+1)^2 patch, centre excluded, row-major (dy outer, dx inner); Hv = H - 2r, Wv = W - 2r; a pixel is valid when its whole
+ * patch is inside the image.
+ *   g_x(p)   = (255 / max_val) (1/C) sum_c x(p,c)        intensity on the 0..255 scale: the constants mean what they mean in the
+ *                                                        literature
+ *   d_x(p,o) = g_x(p+o) - g_x(p)       R_x(p,o) = sqrt(0.81 + d_x^2)       t_x(p,o) = d_x / R_x
+ *   u(p,o)   = t_a - t_b               e = u^2
+ *   dist(p)  = (1/K) sum_o e / (0.1 + e)                 in [0, 1)
+ *   root(p)  = sqrt(dist + eps^2)      rho(p) = dist / (root + eps)        the Charbonnier penalty root - eps, written so that
+ *                                                                          dist == 0 gives exactly 0 whatever the rounding
+ *   census_loss = (1 / (N Hv Wv)) sum over n and the valid p of rho(p)
+ *   loss_accum[0] += weight * census_loss, or = weight * census_loss when mv3d_loss_overwrite_next() is pending on the calling
+ *   thread (the flag is consumed; a recorded call keeps what it saw).  One thread adds, in stream order: no atomics.
+ * grad (optional; NULL = value only) [N,H,W,C] with pixel stride grad_ld >= C receives d(weight * census_loss)/da: stored when
+ * grad_accumulate == 0, one fp32 addition onto what is there when grad_accumulate == 1 (a second differentiated term on one
+ * tensor).  Channels outside the view are never written.
+ *   phi(p,o) = [0.1 / (0.1 + e)^2] 2 u 0.81 / R_a^3      rho'(p) = 1 / (2 root(p))
+ *   dL/dg_a(q) = (1 / (K N Hv Wv)) ( sum_{o : q-o valid} rho'(q-o) phi(q-o, o) - [q valid] rho'(q) sum_o phi(q, o) )
+ *   grad(q,c)  = weight (255 / (max_val C)) dL/dg_a(q)   the same for every channel c
+ * Pixels outside the valid region still receive a gradient as neighbours.  a == b gives a loss of exactly 0 and a gradient of
+ * exactly 0, because u == 0.
+ * Every step is fp32 without contraction in the order metrics.py census_loss_host states (sqrt and division correctly rounded):
+ * the numbers it computes in float32.  The tile sums of rho are kept in double and reduced in a fixed order.  Every gradient
+ * element is written by exactly one thread; the same inputs give the same bits in value and gradient, run after run and under
+ * plan replay; the value is the same bits with and without grad.  The call allocates nothing and keeps no state outside
+ * `workspace` (16-byte aligned, mv3d_census_loss_workspace_bytes() bytes, which is 0 for a shape or radius the entry refuses):
+ * the per-tile sums live there between its two launches (plan labels census_loss_tile, census_loss_final).
+ * MV3D_E_INVAL before any launch: N < 1; radius outside 1..3; H or W < 2r+1; C outside 1..4; H or W > 32768, or
+ * N * ceil(H/32) * ceil(W/32) >= 2^31; a_ld or b_ld < C; grad given and grad_ld < C; grad_accumulate outside {0, 1}; max_val or
+ * eps not finite or <= 0; weight not finite; a, b, loss_accum or workspace null; a, b, loss_accum or grad not 4-byte aligned.
+ * MV3D_E_WORKSPACE: workspace too small or not 16-byte aligned.  On any error loss_accum and grad are left untouched and a
+ * pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_census_loss_workspace_bytes(int N, int H, int W, int C, int radius);
+int mv3d_census_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, int radius, float max_val,
+                     float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* ---- edge-aware flow smoothness: value and gradient with respect to the flow --------------------------------------------
  * flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view works), H, W >= 2; guide (optional; NULL with
