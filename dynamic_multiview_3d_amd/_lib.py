@@ -88,6 +88,8 @@ STATUS_FUNCS = {
     "mv3d_sgd_step": [_i64, _vp, _vp, _vp, _f, _f, _i, _f, _vp],
     "mv3d_sgd_step_dev": [_i64, _vp, _vp, _vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64), _vp],
     "mv3d_fc_wgrad_sgd": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "mv3d_ema_step": [_i64, _vp, _vp, _f, _vp],
+    "mv3d_swap_f32": [_i64, _vp, _vp, _vp],
     "mv3d_grad_finalize_begin": [],
     "mv3d_grad_finalize_add": [_vp, _i64],
     "mv3d_grad_finalize_commit": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -21,6 +21,7 @@ UNITS = {
     "wgrad_tile.hip": [],
     "fc.hip": [],
     "elem.hip": ["-ffp-contract=off"],
+    "ema.hip": ["-ffp-contract=off"],
     "resampler.hip": ["-ffp-contract=off"],
     "process_image.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],

@@ -19,6 +19,7 @@ Data layout in HBM
     contiguous bucket views.
 PyTorch is used for device memory (torch.empty), streams and torch.distributed only.
 """
+import contextlib
 import ctypes as C
 import os
 import math
@@ -31,6 +32,28 @@ from . import _lib
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
 _current = []
+
+EMA_SLOT = 'ExponentialMovingAverage'           # TF's shadow-variable name: <var>/ExponentialMovingAverage
+EMA_COUNTER = EMA_SLOT + '/num_updates'
+
+
+# =============================================================================================== EMA host twins
+def ema_one_minus_decay(decay, n=None):
+    """float32(1 - decay_t), the scalar mv3d_ema_step takes: decay_t = decay, or with tf.train.ExponentialMovingAverage's
+    num_updates = n (the zero-based index of the update) min(decay, (1 + n) / (10 + n)).  Evaluated in double, rounded once."""
+    d = float(decay)
+    if n is not None:
+        d = min(d, (1.0 + float(n)) / (10.0 + float(n)))
+    return np.float32(1.0 - d)
+
+
+def ema_rule(shadow, params, one_minus_decay):
+    """numpy twin of mv3d_ema_step: assign_moving_average(zero_debias=False) on float32 arrays, in TF's order and with one
+    rounding per operation -- d = s - p; u = d * w; s = s - u.  Returns the new shadows (the inputs are left alone)."""
+    s, p = np.asarray(shadow, np.float32), np.asarray(params, np.float32)
+    d = s - p
+    u = d * np.float32(one_minus_decay)
+    return s - u
 
 
 def current_graph():
@@ -620,6 +643,14 @@ class Graph:
         self.dp_mode = 'sharded'        # 'sharded': reduce-scatter -> Adam on 1/world of every bucket -> all-gather; 'allreduce': SUM + redundant Adam
         self.comm_stream = None
         self.bucket_elems = 16 * 1024 * 1024        # 64 MB of fp32 gradients per all-reduce bucket
+        # tf.train.ExponentialMovingAverage of every variable (enable_ema): one flat shadow buffer with the layout of params,
+        # updated by mv3d_ema_step behind each optimiser launch of a train step, on that launch's stream
+        self.ema = None
+        self.ema_decay, self.ema_num_updates, self.ema_updates = None, False, 0
+        self._ema_event = None          # recorded behind an EMA launch the step leaves running on a side stream
+        self._ema_pending = False
+        self._ema_swapped = False       # inside ema_weights(): params holds the shadows and ema the weights
+        self._fc_ranges = []            # flat ranges the fused fc optimiser's stream updates (run_backward_fused)
 
     OPTIMIZERS = ('adam', 'momentum', 'sgd')
 
@@ -698,6 +729,8 @@ class Graph:
             host[v.offset:v.offset + v.size] = v.init(self.rng, v.shape).reshape(-1)
         self.params = torch.from_numpy(host).to(dev)
         self.grads = torch.zeros(off, dtype=torch.float32, device=dev)
+        if self.ema_decay is not None:      # the shadows start as a copy of the variables, as TF initialises them
+            self.ema = self.params.clone()
         # optimiser slots: Adam m and v, one momentum accumulator, or none (gradient descent)
         if self.optimizer not in self.OPTIMIZERS:
             raise ValueError("unknown optimizer %r (have %s)" % (self.optimizer, ', '.join(self.OPTIMIZERS)))
@@ -1096,10 +1129,88 @@ class Graph:
                 self._bias_skip = (len(gaps), (C.c_int64 * max(1, len(gaps)))(*[a for a, _ in gaps] or [0]),
                                    (C.c_int64 * max(1, len(gaps)))(*[b for _, b in gaps] or [0]))
                 self._fwd_wait_idx = self._first_fc_hazard()
+                self._fc_ranges = [tuple(r) for r in skips]      # what the fused kernels and the bias launch update, on their stream
             else:
                 lib.plan_destroy(plan)
         self.upload_optimizer_state()
+        self.reset_ema()
         return self
+
+    # ---------------------------------------------------------------- EMA weights
+    def enable_ema(self, decay, num_updates=False):
+        """tf.train.ExponentialMovingAverage(decay, num_updates).apply(every variable), run behind each train step's optimiser:
+        call before compile().  Graph.ema (flat, the layout of params) holds the shadows, Graph.ema_updates the number of updates
+        made so far (the `num_updates` TF is handed when the switch is on: decay_t = min(decay, (1 + n) / (10 + n)))."""
+        decay = float(decay)
+        if not np.isfinite(decay) or not 0.0 < decay < 1.0:
+            raise ValueError("enable_ema: decay must be finite and in (0, 1), got %r" % (decay,))
+        if self.plan_fwd is not None:
+            raise RuntimeError("enable_ema: call it before compile()")
+        self.ema_decay, self.ema_num_updates = decay, bool(num_updates)
+        if self.finalized and self.ema is None:
+            self.ema = self.params.clone()
+
+    def reset_ema(self):
+        """Shadows := the variables as they are now, update counter := 0 (TF's initial state; call it after set_variables()
+        when the new values are a fresh start rather than a step of this run).  No-op with EMA off."""
+        if self.ema is None:
+            return
+        self._check_not_swapped('reset_ema')
+        self._settle()
+        self.ema.copy_(self.params)
+        self.ema_updates = 0
+
+    def _check_not_swapped(self, what):
+        if self._ema_swapped:
+            raise RuntimeError("%s inside ema_weights(): the parameter buffer holds the averaged weights" % what)
+
+    def _ema_range(self, lo, hi, stream):
+        """mv3d_ema_step over the flat range [lo, hi) on `stream`, behind the optimiser launch that updated it there."""
+        w = float(ema_one_minus_decay(self.ema_decay, self.ema_updates if self.ema_num_updates else None))
+        self.lib.ema_step(hi - lo, self.ema.data_ptr() + lo * 4, self.params.data_ptr() + lo * 4, w, stream)
+
+    def _ema_side(self, stream):
+        """The step leaves an EMA launch running on `stream` (a torch stream other than the current one): readers of Graph.ema
+        and the next writers of params on other streams wait for this event (_settle()); the forward pass does not."""
+        if self._ema_event is None:
+            self._ema_event = torch.cuda.Event()
+        self._ema_event.record(stream)
+        self._ema_pending = True
+
+    def get_ema_variables(self):
+        """The shadows, like get_variables(): one host array per variable (a variable without a gradient equals its shadow)."""
+        if self.ema is None:
+            raise RuntimeError("get_ema_variables: EMA is off (Graph.enable_ema / conf['ema_decay'])")
+        self._check_not_swapped('get_ema_variables')
+        self._settle()
+        return OrderedDict((k, self.ema[v.offset:v.offset + v.size].view(v.shape).detach().cpu().numpy().copy())
+                           for k, v in self.variables.items())
+
+    def _swap_ema(self):
+        self._settle()
+        if torch.device(self.device).type == 'cuda':
+            self.lib.swap_f32(self.flat_size, self.params.data_ptr(), self.ema.data_ptr(), self._stream_ptr())
+        else:
+            tmp = self.params.clone()
+            self.params.copy_(self.ema)
+            self.ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with g.ema_weights(): forward passes (evaluate, visualize) run on the averaged weights.  params and ema are exchanged
+        in place (mv3d_swap_f32: no third buffer) and exchanged back on exit, also when the body raises; train_step() and the
+        checkpoint calls raise RuntimeError inside.  Conv filters are re-converted by the first launch of every forward pass
+        and fc matrices at each use, so nothing else has to be invalidated."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights: EMA is off (Graph.enable_ema / conf['ema_decay'])")
+        self._check_not_swapped('ema_weights')
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            self._swap_ema()
 
     def _finalize_commit(self):
         """Close the open mv3d_grad_finalize collection: one launch on the filter-gradient stream that sums the collected layers'
@@ -1186,11 +1297,19 @@ class Graph:
                 idx = min(idx, self._fwd_first_op[id(n)])
         return idx
 
-    def _settle(self):
+    def _settle_fc(self):
         """Order the current stream behind a fused fc optimiser still in flight from the last train step."""
         if self._fc_pending:
             torch.cuda.current_stream(self.device).wait_event(self._fc_event)
             self._fc_pending = False
+
+    def _settle(self):
+        """_settle_fc(), and behind the EMA launch that follows that optimiser on its stream (the forward pass waits for the
+        optimiser alone: it reads the weights, never the shadows)."""
+        self._settle_fc()
+        if self._ema_pending:
+            torch.cuda.current_stream(self.device).wait_event(self._ema_event)
+            self._ema_pending = False
 
     settle = _settle        # public name: call before touching Graph.params / adam_m / adam_v / accum / grads directly
 
@@ -1198,10 +1317,10 @@ class Graph:
         st = self._stream_ptr()
         if self._fc_pending and 0 < self._pending_idx < self.n_launch_fwd:
             self.lib.plan_run_range(self.plan_fwd, 0, self._pending_idx, st)
-            self._settle()
+            self._settle_fc()
             self.lib.plan_run_range(self.plan_fwd, self._pending_idx, self.n_launch_fwd, st)
             return
-        self._settle()
+        self._settle_fc()
         self.lib.plan_run(self.plan_fwd, st)
 
     def begin_side(self, cls=1):
@@ -1281,6 +1400,9 @@ class Graph:
         self._settle()
         self._opt_range(0, self.flat_size, self._stream_ptr())
         self._adam_advance()
+        if self.ema is not None:
+            self._ema_range(0, self.flat_size, self._stream_ptr())
+            self.ema_updates += 1
 
     apply_adam = apply_optimizer
 
@@ -1314,6 +1436,22 @@ class Graph:
         if not self._finalized_in_plan:          # otherwise the plan's last launch (grad_finalize_<kind>) was the optimiser of everything else
             self._opt_range(0, self.flat_size, st, (len(self._skip_lo), self._skip_lo, self._skip_hi))
         self._adam_advance(st, both=False)
+        if self.ema is not None:
+            # every range behind its optimiser, on that optimiser's stream: the fused matrices and their layers' biases on the fc
+            # stream (behind _fc_event: the next forward pass does not wait for the EMA), the rest on the main stream (which has
+            # joined the stream of the grad_finalize launches).  The next step's writers of params fork from the main stream or
+            # sit on the fc stream, so they are behind these reads.
+            at = 0
+            for a, b in self._fc_ranges:
+                if a > at:
+                    self._ema_range(at, a, st)
+                self._ema_range(a, b, fc_stream)
+                at = b
+            if at < self.flat_size:
+                self._ema_range(at, self.flat_size, st)
+            if pipelined:
+                self._ema_side(fcq)
+            self.ema_updates += 1
 
     def run_backward_with_adam(self):
         """Single-GPU reverse pass with the optimiser folded in: the backward plan is issued bucket by bucket
@@ -1346,11 +1484,15 @@ class Graph:
                 if self.adam_timing is not None:
                     e1.record(self.adam_stream)
                     self.adam_timing.append((e0, e1))
+                if self.ema is not None:                # behind the slice's optimiser, on its stream (joined below)
+                    self._ema_range(plo, phi, self.adam_stream.cuda_stream)
             pending = []
         main.wait_stream(self.adam_stream)
         for st in (self.side_streams or []):
             main.wait_stream(st)
         self._adam_advance(main.cuda_stream)
+        if self.ema is not None:
+            self.ema_updates += 1
 
     run_backward_with_optimizer = run_backward_with_adam
 
@@ -1429,9 +1571,17 @@ class Graph:
                 self._pending_idx = late[0][0]
         if with_adam:
             self._adam_advance()
+            if self.ema is not None:
+                # ONE launch over the whole buffer on the communication stream, behind the last all-gather (late ones included)
+                # and behind _fc_event: every rank keeps the complete shadow of its (bit-identical) parameters
+                self._ema_range(0, self.flat_size, cs)
+                if on_gpu:
+                    self._ema_side(self.comm_stream)
+                self.ema_updates += 1
 
     def train_step(self):
-        """forward + loss + reverse pass + (all-reduce) + optimiser; returns the device loss scalar."""
+        """forward + loss + reverse pass + (all-reduce) + optimiser (+ EMA of the weights); returns the device loss scalar."""
+        self._check_not_swapped('train_step')
         self.run_forward()
         if self.world_size > 1:
             self.run_backward_overlapped(with_adam=True)
@@ -1490,7 +1640,10 @@ class Graph:
 
     def state_dict(self):
         """TF-Saver-style names: <var> and the active optimiser's slots -- <var>/Adam, <var>/Adam_1, beta1_power, beta2_power
-        (Adam), <var>/Momentum (Momentum), nothing else (GD) -- (train.py:70-71 saves GLOBAL_VARIABLES)."""
+        (Adam), <var>/Momentum (Momentum), nothing else (GD) -- (train.py:70-71 saves GLOBAL_VARIABLES).  With EMA on also
+        <var>/ExponentialMovingAverage for EVERY variable (TF's shadow variables) and the update counter
+        ExponentialMovingAverage/num_updates; every data-parallel rank holds the complete shadows."""
+        self._check_not_swapped('state_dict')
         self._settle()
         if self.world_size > 1 and getattr(self, '_slots_sharded', False):
             raise RuntimeError("sharded data-parallel step: this rank holds 1/%d of the optimiser slots; call "
@@ -1502,15 +1655,37 @@ class Graph:
             if v.has_grad:
                 for name, buf in slots:
                     sd[k + '/' + name] = buf[v.offset:v.offset + v.size].view(v.shape).detach().cpu().clone()
+            if self.ema is not None:
+                sd[k + '/' + EMA_SLOT] = self.ema[v.offset:v.offset + v.size].view(v.shape).detach().cpu().clone()
         if self.optimizer == 'adam':
             sd['beta1_power'] = torch.tensor(float(self.beta1_power))
             sd['beta2_power'] = torch.tensor(float(self.beta2_power))
+        if self.ema is not None:
+            sd[EMA_COUNTER] = torch.tensor(float(self.ema_updates))
         return sd
 
     def load_state_dict(self, sd):
+        """Restores what state_dict() names; KeyError on a missing or unexpected entry.  With EMA on, a checkpoint that carries
+        every shadow and the counter restores them; one that carries none is a resume that turns the switch on (shadows := the
+        restored variables, counter := 0); one that carries some of them raises KeyError.  With EMA off shadow entries are
+        unexpected like any other."""
+        self._check_not_swapped('load_state_dict')
         self._settle()
         slots = self._slots()
         names = {n for n, _ in slots}
+        ema_keys = []
+        if self.ema is not None:
+            ema_keys = [k + '/' + EMA_SLOT for k in self.variables] + [EMA_COUNTER]
+            have = [k for k in ema_keys if k in sd]
+            if have and len(have) != len(ema_keys):
+                raise KeyError("checkpoint holds %d of the model's %d EMA entries (<var>/%s and %s): missing %s"
+                               % (len(have), len(ema_keys), EMA_SLOT, EMA_COUNTER, [k for k in ema_keys if k not in sd][:8]))
+            sd = OrderedDict(sd)
+            ema_sd = {k: sd.pop(k) for k in have}
+            bad_ema = [k for k, v in self.variables.items() if k + '/' + EMA_SLOT in ema_sd and
+                       tuple(ema_sd[k + '/' + EMA_SLOT].shape) != tuple(v.shape)]
+            if bad_ema:
+                raise KeyError("checkpoint does not match the model: shape mismatch of the EMA shadows of %s" % bad_ema[:8])
         missing = [k for k in self.variables if k not in sd]
         if self.optimizer == 'momentum':        # the accumulator is what identifies a Momentum checkpoint (Adam's: the beta powers)
             missing += [k + '/Momentum' for k, v in self.variables.items() if v.has_grad and k + '/Momentum' not in sd]
@@ -1530,6 +1705,14 @@ class Graph:
         if self.optimizer == 'adam':
             self.beta1_power = np.float32(float(sd['beta1_power']))
             self.beta2_power = np.float32(float(sd['beta2_power']))
+        if self.ema is not None:
+            if ema_sd:
+                for k, v in self.variables.items():
+                    self.ema[v.offset:v.offset + v.size].view(v.shape).copy_(ema_sd[k + '/' + EMA_SLOT])
+                self.ema_updates = int(round(float(ema_sd[EMA_COUNTER])))
+            else:
+                self.ema.copy_(self.params)
+                self.ema_updates = 0
         self.upload_optimizer_state()
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import tf_checkpoint
-from .graph import Graph
+from .graph import Graph, ema_one_minus_decay, ema_rule      # noqa: F401  (the numpy twins of mv3d_ema_step are part of this module's interface)
 
 
 class Saver:
@@ -98,6 +98,23 @@ def optimizer_from_conf(conf, learning_rate, **adam_kw):
             raise ValueError("conf['optimizer'] = 'momentum' needs conf['momentum']")
         return MomentumOptimizer(learning_rate, float(conf['momentum']), bool(conf.get('use_nesterov', False)))
     raise ValueError("unknown conf['optimizer'] %r (have 'adam', 'momentum', 'sgd')" % (name,))
+
+
+def ema_from_conf(conf):
+    """(decay or None, num_updates) of the EMA-weights switch: conf['ema_decay'] absent, None or 0 = off (the graph then records
+    and launches exactly what it did without the key); otherwise tf.train.ExponentialMovingAverage's decay, finite and in (0, 1).
+    conf['ema_num_updates'] (default False) hands TF's num_updates to it: decay_t = min(decay, (1 + n) / (10 + n)).  Raises
+    ValueError on a value out of range, before any device work."""
+    decay = conf.get('ema_decay')
+    num_updates = bool(conf.get('ema_num_updates', False))
+    if decay is None or (not isinstance(decay, bool) and decay == 0):
+        return None, num_updates
+    if isinstance(decay, bool):
+        raise ValueError("conf['ema_decay'] must be a number in (0, 1), got %r" % (decay,))
+    decay = float(decay)
+    if not np.isfinite(decay) or not 0.0 < decay < 1.0:
+        raise ValueError("conf['ema_decay'] must be finite and in (0, 1) (or 0 / None for off), got %r" % (conf['ema_decay'],))
+    return decay, num_updates
 
 
 def ssim_weight_from_conf(conf):
@@ -260,13 +277,23 @@ class ModelBase(object):
 
     def _make_graph(self, device, seed):
         self._check_conf()
+        ema_from_conf(self.conf)        # a bad conf['ema_decay'] raises here, before any device work
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 
     def _finish(self, build_loss):
         self.t_vars = list(self.graph.variables.keys())
         self.saver = Saver(self.graph)
+        # EMA weights are a property of the graph, not of the loss: a build_loss=False model holds the shadows too, so that a
+        # checkpoint can be restored and rendered with them
+        decay, num_updates = ema_from_conf(self.conf)
+        if decay is not None:
+            self.graph.enable_ema(decay, num_updates)
         self.graph.compile()
+
+    def ema_weights(self):
+        """Context manager: forward passes inside run on the averaged weights (Graph.ema_weights)."""
+        return self.graph.ema_weights()
 
     # ---- sess.run replacements
     def feed(self, **feeds):
@@ -297,7 +324,29 @@ class ModelBase(object):
         TARGET as the reader / the reference's loader produces it; each model class states where its value comes from."""
         raise NotImplementedError("%s defines no eval_pairs()" % type(self).__name__)
 
-    def evaluate(self, data, num_batches=19):
+    def evaluate(self, data, num_batches=19, weights=None):
+        """_evaluate() on the weights asked for: 'raw' (the variables), 'ema' (the averaged weights, conf['ema_decay'] must be on)
+        or None = 'ema' when the switch is on, else 'raw'.  With the switch on the result also names them: 'weights': 'ema' | 'raw';
+        with it off the result is _evaluate()'s alone."""
+        have = getattr(self.graph, 'ema', None) is not None
+        if weights is None:
+            weights = 'ema' if have else 'raw'
+        if weights not in ('ema', 'raw'):
+            raise ValueError("evaluate: weights must be 'ema', 'raw' or None, got %r" % (weights,))
+        if weights == 'ema' and not have:
+            raise ValueError("evaluate: weights='ema' needs conf['ema_decay']")
+        if int(num_batches) < 1:
+            raise ValueError("evaluate: num_batches must be at least 1")
+        if weights == 'ema':
+            with self.graph.ema_weights():
+                result = self._evaluate(data, num_batches)
+        else:
+            result = self._evaluate(data, num_batches)
+        if have:
+            result['weights'] = weights
+        return result
+
+    def _evaluate(self, data, num_batches=19):
         """The quantitative counterpart of mv3d.test() (mv3d/nobg_dm.py:117-149): forward(**data.next()) num_batches times
         (19 = the reference's test_iter), the loss averaged over the batches (:143-145), and per-image L1 / PSNR / SSIM of every
         eval_pairs() entry averaged over the images (metrics.py; PSNR is averaged per image, an image with mse == 0 makes it inf).

@@ -18,6 +18,8 @@ test_iter, mv3d/nobg_dm.py:118) of the `test` split -- or of synthetic batches w
 conf['event_log_dir'] (default output_dir): `training_loss` and `val_loss` where the JSON-lines log gets them, and with
 --evaluate `test_loss` and the metrics at the checkpoint's iteration.  Without the flag only the JSON-lines log is written.
 Not ported: image and histogram summaries.
+With conf['ema_decay'] the checkpoints carry the averaged weights (<var>/ExponentialMovingAverage), and --evaluate and --visualize
+run on them; --raw_weights opts out.  The periodic val_loss during training stays on the raw weights.
 """
 import argparse
 import importlib
@@ -112,15 +114,16 @@ def _event_writer(conf):
     return FileWriter(conf.get('event_log_dir') or conf['output_dir'])
 
 
-def evaluate_checkpoint(model, conf, name, data, num_batches, event_log=False, write=True):
+def evaluate_checkpoint(model, conf, name, data, num_batches, event_log=False, write=True, weights=None):
     """--evaluate: restore output_dir/<name>, model.evaluate() over num_batches batches of `data`, print the result and write
     output_dir/eval_<name>.json; with event_log also `test_loss` (mv3d/nobg_dm.py:148-149) and every metric as scalars at the
-    iteration the checkpoint's name ends in (0 when it ends in none, like the final `model`)."""
+    iteration the checkpoint's name ends in (0 when it ends in none, like the final `model`).  weights: model.evaluate()'s
+    (None = the averaged weights when conf['ema_decay'] is on, 'raw' = the variables)."""
     import re
     path = conf['output_dir'] + '/' + name
     model.saver.restore(None, path)
     print('restore done.')
-    result = model.evaluate(data, num_batches)
+    result = model.evaluate(data, num_batches) if weights is None else model.evaluate(data, num_batches, weights=weights)
     m = re.match('.*?([0-9]+)$', name)
     result['iteration'] = int(m.group(1)) if m else 0
     result['checkpoint'] = name
@@ -132,7 +135,7 @@ def evaluate_checkpoint(model, conf, name, data, num_batches, event_log=False, w
         if event_log:
             events = _event_writer(conf)
             for key, value in result.items():
-                if key in ('images', 'iteration', 'checkpoint'):
+                if key in ('images', 'iteration', 'checkpoint', 'weights'):
                     continue
                 log_value(events, value, 'test_loss' if key == 'loss' else key, result['iteration'])
             events.close()
@@ -150,6 +153,9 @@ def main(argv=None):
     ap.add_argument('--evaluate', default='', help='model within hyperparameter folder to score on the test split (loss, L1, PSNR, SSIM)')
     ap.add_argument('--eval_batches', type=int, default=19, help='batches --evaluate scores (the reference tests 19)')
     ap.add_argument('--event_log', action='store_true', help='also write the scalars as TensorFlow event files')
+    ap.add_argument('--raw_weights', action='store_true',
+                    help="--evaluate / --visualize on the variables themselves, not on the averaged weights of conf['ema_decay'] "
+                         "(the periodic val_loss during training is always computed on the raw weights)")
     FLAGS = ap.parse_args(argv)
     if FLAGS.visualize and FLAGS.evaluate:
         ap.error('--visualize and --evaluate exclude each other')
@@ -201,12 +207,16 @@ def main(argv=None):
         print('-------------------------------------------------------------------')
         saver.restore(None, conf['visualize'])
         print('restore done.')
-        model.visualize(None, **train_data.next())
+        if model.graph.ema is not None and not FLAGS.raw_weights:
+            with model.ema_weights():
+                model.visualize(None, **train_data.next())
+        else:
+            model.visualize(None, **train_data.next())
         return model
 
     if FLAGS.evaluate:
         return evaluate_checkpoint(model, conf, FLAGS.evaluate, train_data, FLAGS.eval_batches, FLAGS.event_log and rank == 0,
-                                   write=rank == 0)
+                                   write=rank == 0, weights='raw' if FLAGS.raw_weights else None)
 
     itr_0 = 0
     if FLAGS.pretrained is not None:

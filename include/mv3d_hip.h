@@ -465,6 +465,18 @@ int mv3d_sgd_step_dev(int64_t count, void* p, const void* g, void* accum, const 
 int mv3d_fc_wgrad_sgd(int B, int in, int out, const void* x, int x_ld, const void* dy, int dy_ld, void* M, void* accum,
                       void* db, const void* sgd_state, void* stream);
 
+/* ---- EMA weights: tf.train.ExponentialMovingAverage (moving_averages.assign_moving_average, zero_debias=False) -------------
+ * Per element, fp32, in TF's order and without contraction (bit-exact against numpy):
+ *   d = s - p;  u = d * one_minus_decay;  s = s - u
+ * over `count` >= 1 floats (a scalar tail takes count & 3).  params is only read.  one_minus_decay is float32(1 - decay_t),
+ * rounded once by the caller, and must lie in [0, 1].  Both pointers 16-byte aligned.  12 B of HBM traffic per parameter
+ * (two loads, one store: the traffic of mv3d_sgd_step without a slot).  Kernel label: ema_kernel. */
+int mv3d_ema_step(int64_t count, void* shadow, const void* params, float one_minus_decay, void* stream);
+/* Exchanges two disjoint buffers of `count` >= 1 floats in place, bit for bit (NaN payloads included): the averaged weights
+ * take the place of the weights without a third buffer.  Both pointers 16-byte aligned; a == b or an overlap is refused.
+ * Kernel label: swap_kernel. */
+int mv3d_swap_f32(int64_t count, void* a, void* b, void* stream);
+
 /* ---- gradient finalisation: the slab reductions of ALL filter gradients (+ their optimiser update) in one launch ------------
  * Replaces, on the recorded single-GPU step, the per-layer partial-filter reductions behind tf.gradients' Conv2DBackpropFilter
  * ops and the tf.train.AdamOptimizer ApplyAdam ops of every variable that is not an fc matrix (appearance_flow_model.py:77).
