@@ -90,6 +90,7 @@ STATUS_FUNCS = {
     "mv3d_fc_wgrad_sgd": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "mv3d_ema_step": [_i64, _vp, _vp, _f, _vp],
     "mv3d_swap_f32": [_i64, _vp, _vp, _vp],
+    "mv3d_grad_clip_scale": [_i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
     "mv3d_grad_finalize_begin": [],
     "mv3d_grad_finalize_add": [_vp, _i64],
     "mv3d_grad_finalize_commit": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -135,6 +136,7 @@ OTHER_FUNCS = {
     "mv3d_census_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_multiscale_warp_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "mv3d_grad_clip_workspace_bytes": (_sz, [_i64]),
     "mv3d_crc32c": (C.c_uint32, [_vp, _sz]),
     "mv3d_set_diagnostics": (C.c_int, [_i]),
     "mv3d_set_wgrad_cus": (C.c_int, [_i]),

@@ -9,9 +9,11 @@
 //                 B2 = (s2 - den0) + c2.  mv3d_image_metrics and mv3d_ssim_loss form S = (A1 / B1) (A2 / B2) from this one
 //                 expression, so their S is the same number
 //   sums          double.  A wave adds its lanes as a butterfly (offsets 32, 16 .. 1), a workgroup of four waves adds the wave sums
-//                 as ((w0 + w1) + w2) + w3, a final kernel strides over the tiles: fixed orders, the same bits on every run
+//                 as ((w0 + w1) + w2) + w3 (wave_sum / block_sum / block_total, in sum_common.h since the gradient-norm unit shares
+//                 them), a final kernel strides over the tiles: fixed orders, the same bits on every run
 #pragma once
 #include "common.h"
+#include "sum_common.h"
 #include <cmath>
 #include <initializer_list>
 #include <utility>
@@ -21,29 +23,9 @@ namespace mv3d {
 constexpr int IMG_TAPS = 11;                       // Gaussian window, sigma 1.5
 constexpr int IMG_TILE = 32;                       // tile side of the two SSIM entries
 constexpr int IMG_MAX_SIDE = 32768;                // ... and their largest H, W: H * W < 2^31 pixels per image
-constexpr int IMG_THREADS = 256;                   // four waves: what block_sum and tile_sums_final are written for
+constexpr int IMG_THREADS = SUM_THREADS;           // four waves: what block_sum (sum_common.h) and tile_sums_final are written for
 
 // ---- device ---------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// K sums over the workgroup's 256 threads: the wave sums land in s_red[q * 4 + wave] (K * 4 doubles), then a barrier; any thread
-// may then read block_total(s_red, q).
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* s_red, int tid) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        const double s = wave_sum(v[q]);
-        if ((tid & 63) == 0) s_red[q * 4 + (tid >> 6)] = s;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ double block_total(const double* s_red, int q) {
-    return ((s_red[q * 4] + s_red[q * 4 + 1]) + s_red[q * 4 + 2]) + s_red[q * 4 + 3];
-}
 
 // One item of a window pass: G neighbouring outputs of Q quantities from G + 10 inputs.  load(j, v) fills v with the Q values at
 // input j; acc[q][o] becomes the window sum whose first input is o.  Fully unrolled: acc and the taps stay in registers.

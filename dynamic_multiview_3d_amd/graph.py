@@ -56,6 +56,49 @@ def ema_rule(shadow, params, one_minus_decay):
     return s - u
 
 
+# =============================================================================================== gradient-clipping host twin
+GN_CHUNK = 16384                                # floats per chunk of mv3d_grad_clip_scale (csrc/grad_norm.hip): 256 threads x 16 float4
+
+
+def _block_sum_rule(v):
+    """block_sum / block_total of csrc/sum_common.h over the last axis (256 doubles, one per thread): the xor butterfly inside each
+    wave of 64 (lane 0's value: the halves added pairwise, offsets 32 .. 1), then ((w0 + w1) + w2) + w3."""
+    v = v.reshape(v.shape[:-1] + (4, 64))
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v[..., :off] + v[..., off:2 * off]
+    w = v[..., 0]
+    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+
+
+def grad_clip_rule(g, pre_scale, clip_norm):
+    """numpy twin of mv3d_grad_clip_scale, in the order include/mv3d_hip.h states: (norm, scale, gscale) as float32, the device's
+    out[0], out[1] and slot 6 of the optimiser records, bit for bit.  g: the flat float32 gradient buffer; pre_scale: float32(1 /
+    world size); clip_norm: > 0, inf = measure only."""
+    g = np.asarray(g, np.float32).reshape(-1)
+    pre, clip = np.float32(pre_scale), np.float32(clip_norm)
+    nchunk = -(-g.size // GN_CHUNK)
+    x = np.zeros(nchunk * GN_CHUNK, np.float64)             # elements past the count are 0
+    x[:g.size] = g
+    with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
+        x *= x                                              # exact: 24 x 24 bits
+        x = np.ascontiguousarray(x.reshape(nchunk, 16, 256, 4).transpose(1, 3, 0, 2))   # [chunk, float4 k, thread, component] -> [k, component, chunk, thread]
+        acc = np.zeros((nchunk, 256), np.float64)
+        for k in range(16):                                 # 64 sequential adds per thread: k = 0 .. 15, then x, y, z, w
+            for c in range(4):
+                acc = acc + x[k, c]
+        part = _block_sum_rule(acc)                         # one double per chunk
+        rounds = -(-nchunk // 256)                          # final kernel: thread t adds partials t, t + 256, ..
+        p = np.zeros(rounds * 256, np.float64)
+        p[:nchunk] = part
+        acc = np.zeros(256, np.float64)
+        for row in p.reshape(rounds, 256):
+            acc = acc + row
+        S = _block_sum_rule(acc)
+        n = np.float32(np.sqrt(S)) * pre
+        s = clip / n if n > clip else np.float32(1.0)       # NaN compares false; n = inf gives 0
+        return np.float32(n), np.float32(s), np.float32(pre * s)
+
+
 def current_graph():
     if not _current:
         raise RuntimeError("no Graph is active: build models inside `with Graph(...) as g:`")
@@ -651,6 +694,11 @@ class Graph:
         self._ema_pending = False
         self._ema_swapped = False       # inside ema_weights(): params holds the shadows and ema the weights
         self._fc_ranges = []            # flat ranges the fused fc optimiser's stream updates (run_backward_fused)
+        # global-norm gradient clipping (enable_grad_clip): mv3d_grad_clip_scale over the flat gradient buffer writes the gradient
+        # scale of both optimiser records just before the optimiser runs; inf = measure the norm only
+        self.clip_norm = None
+        self.clip_buf = None            # device [norm, scale] of the last step
+        self._clip_ws, self._clip_ws_bytes = None, 0
 
     OPTIMIZERS = ('adam', 'momentum', 'sgd')
 
@@ -731,6 +779,8 @@ class Graph:
         self.grads = torch.zeros(off, dtype=torch.float32, device=dev)
         if self.ema_decay is not None:      # the shadows start as a copy of the variables, as TF initialises them
             self.ema = self.params.clone()
+        if self.clip_norm is not None:
+            self._alloc_grad_clip()
         # optimiser slots: Adam m and v, one momentum accumulator, or none (gradient descent)
         if self.optimizer not in self.OPTIMIZERS:
             raise ValueError("unknown optimizer %r (have %s)" % (self.optimizer, ', '.join(self.OPTIMIZERS)))
@@ -1053,7 +1103,8 @@ class Graph:
         self.plan_bwd_fused = None
         self._fused_vars = []
         self._fused_nodes = []
-        if self.fuse_fc_adam and self.lr is not None and any(isinstance(n, LinearNode) for n in self.nodes):
+        # (not with gradient clipping: the fused kernels never write the fc gradients to memory, and the norm needs all of them)
+        if self.fuse_fc_adam and self.clip_norm is None and self.lr is not None and any(isinstance(n, LinearNode) for n in self.nodes):
             for t, (gw, gm) in zip(self.tensors, flags_after_forward):
                 t.grad_written, t.grad_masked = gw, gm
             plan = lib.plan_create()
@@ -1211,6 +1262,61 @@ class Graph:
         finally:
             self._ema_swapped = False
             self._swap_ema()
+
+    # ---------------------------------------------------------------- global-norm gradient clipping
+    def enable_grad_clip(self, clip_norm):
+        """Clip the gradient of every train step to the global L2 norm clip_norm (finite, > 0), or with math.inf only measure the
+        norm: call before compile().  A step then runs the schedule in which the whole gradient exists before the first update
+        (train_step); grad_norm() reads the step's [norm, scale]."""
+        c = float(clip_norm)
+        with np.errstate(over='ignore', under='ignore'):
+            c32 = float(np.float32(c))                  # what the kernel is handed
+        if isinstance(clip_norm, bool) or not c > 0.0 or (math.isfinite(c) and not 0.0 < c32 < math.inf):
+            raise ValueError("enable_grad_clip: clip_norm must be > 0 and a finite float32, or inf to measure only, got %r" % (clip_norm,))
+        if self.plan_fwd is not None:
+            raise RuntimeError("enable_grad_clip: call it before compile()")
+        self.clip_norm = c
+        if self.finalized and self.clip_buf is None:
+            self._alloc_grad_clip()
+
+    def _alloc_grad_clip(self):
+        self.clip_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self._clip_ws_bytes = int(self.lib.grad_clip_workspace_bytes(self.flat_size))
+        self._clip_ws = torch.empty(max(self._clip_ws_bytes // 8, 2), dtype=torch.float64, device=self.device)
+
+    def clip_gradients(self):
+        """mv3d_grad_clip_scale over the whole flat gradient buffer on the main stream, between the reverse pass (and the
+        all-reduce) and the optimiser: the norm of the averaged gradient (pre_scale = float32(1 / world size)) and the clip scale
+        go to grad_norm(), pre_scale * scale into the gradient-scale slot of both optimiser records.  The padding between
+        variables and the ranges of variables without a gradient are zero (grads is torch.zeros and nothing writes there; a SUM
+        over ranks keeps them zero), so the sum over [0, flat_size) is the sum over the gradients."""
+        if self.clip_norm is None:
+            raise RuntimeError("clip_gradients: gradient clipping is off (Graph.enable_grad_clip / conf['grad_clip_norm'])")
+        self._settle()
+        self.lib.grad_clip_scale(self.flat_size, self.grads.data_ptr(), float(np.float32(1.0 / self.world_size)), self.clip_norm,
+                                 self.clip_buf.data_ptr(), self.opt_state.data_ptr(), self.opt_state.data_ptr() + 32,
+                                 self._clip_ws.data_ptr(), self._clip_ws_bytes, self._stream_ptr())
+
+    def grad_norm(self):
+        """The device tensor [norm, scale] of the last clipped step: the L2 norm of the averaged gradient before clipping and the
+        factor the optimiser applied (1 where it did not clip).  Converting it to Python floats is the caller's synchronisation."""
+        if self.clip_buf is None:
+            raise RuntimeError("grad_norm: gradient clipping is off (Graph.enable_grad_clip / conf['grad_clip_norm'])")
+        return self.clip_buf
+
+    def run_backward_clipped(self, data_parallel=None):
+        """Reverse pass, norm, optimiser -- the step with gradient clipping.  The whole gradient exists before the first update:
+        single GPU the plain reverse pass; data parallel (default: world size > 1) the bucketed all-reduce of
+        run_backward_overlapped, overlapped with the pass as ever, in either dp_mode -- every rank then reduces the same summed
+        buffer in the same order, so the scale and the weights stay bit-identical across ranks and every rank holds complete
+        optimiser slots.  The fused, finalize-fused, overlapped and sharded optimiser schedules need the update inside the pass
+        and are not used."""
+        if self.world_size > 1 if data_parallel is None else data_parallel:
+            self.run_backward_overlapped(with_adam=False)
+        else:
+            self.run_backward()
+        self.clip_gradients()
+        self.apply_optimizer()
 
     def _finalize_commit(self):
         """Close the open mv3d_grad_finalize collection: one launch on the filter-gradient stream that sums the collected layers'
@@ -1583,7 +1689,9 @@ class Graph:
         """forward + loss + reverse pass + (all-reduce) + optimiser (+ EMA of the weights); returns the device loss scalar."""
         self._check_not_swapped('train_step')
         self.run_forward()
-        if self.world_size > 1:
+        if self.clip_norm is not None:
+            self.run_backward_clipped()
+        elif self.world_size > 1:
             self.run_backward_overlapped(with_adam=True)
         elif self.plan_bwd_fused is not None:
             self.run_backward_fused()

@@ -13,6 +13,7 @@ import torch
 
 from . import tf_checkpoint
 from .graph import Graph, ema_one_minus_decay, ema_rule      # noqa: F401  (the numpy twins of mv3d_ema_step are part of this module's interface)
+from .graph import grad_clip_rule                            # noqa: F401  (... and the twin of mv3d_grad_clip_scale)
 
 
 class Saver:
@@ -115,6 +116,25 @@ def ema_from_conf(conf):
     if not np.isfinite(decay) or not 0.0 < decay < 1.0:
         raise ValueError("conf['ema_decay'] must be finite and in (0, 1) (or 0 / None for off), got %r" % (conf['ema_decay'],))
     return decay, num_updates
+
+
+def grad_clip_from_conf(conf):
+    """The clip norm Graph.enable_grad_clip takes, or None for off (the graph then allocates, records and launches exactly what it
+    did without the keys).  conf['grad_clip_norm'] = c, finite and > 0, clips every step's gradient to the global L2 norm c;
+    conf['grad_norm_log'] = True without a clip norm only measures (math.inf); absent, None, 0 or False is off.  A bool, a
+    negative value, NaN or inf for grad_clip_norm raises ValueError, before any device work."""
+    import math
+    c = conf.get('grad_clip_norm')
+    if isinstance(c, bool):
+        raise ValueError("conf['grad_clip_norm'] must be a number > 0 (or 0 / None for off), got %r" % (c,))
+    if c is None or c == 0:
+        return math.inf if conf.get('grad_norm_log') else None
+    c = float(c)
+    with np.errstate(over='ignore', under='ignore'):
+        c32 = float(np.float32(c))                  # what the kernel is handed
+    if not math.isfinite(c) or not c > 0.0 or not 0.0 < c32 < math.inf:
+        raise ValueError("conf['grad_clip_norm'] must be finite (as a float32) and > 0 (or 0 / None for off), got %r" % (conf['grad_clip_norm'],))
+    return c
 
 
 def ssim_weight_from_conf(conf):
@@ -278,6 +298,7 @@ class ModelBase(object):
     def _make_graph(self, device, seed):
         self._check_conf()
         ema_from_conf(self.conf)        # a bad conf['ema_decay'] raises here, before any device work
+        grad_clip_from_conf(self.conf)  # ... and a bad conf['grad_clip_norm']
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 
@@ -289,6 +310,9 @@ class ModelBase(object):
         decay, num_updates = ema_from_conf(self.conf)
         if decay is not None:
             self.graph.enable_ema(decay, num_updates)
+        clip = grad_clip_from_conf(self.conf)
+        if clip is not None and build_loss:     # a property of the train step: a model without a loss has no gradient
+            self.graph.enable_grad_clip(clip)
         self.graph.compile()
 
     def ema_weights(self):

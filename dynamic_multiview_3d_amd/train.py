@@ -20,6 +20,8 @@ conf['event_log_dir'] (default output_dir): `training_loss` and `val_loss` where
 Not ported: image and histogram summaries.
 With conf['ema_decay'] the checkpoints carry the averaged weights (<var>/ExponentialMovingAverage), and --evaluate and --visualize
 run on them; --raw_weights opts out.  The periodic val_loss during training stays on the raw weights.
+With conf['grad_clip_norm'] (or conf['grad_norm_log']) the lines written every 10th iteration also carry `grad_norm` and
+`grad_clip_scale` of that step, in the JSON-lines log and, with --event_log, as scalars.
 """
 import argparse
 import importlib
@@ -107,6 +109,16 @@ class SyntheticData:
         b = self.pool[self.i % len(self.pool)]
         self.i += 1
         return b
+
+
+def training_log_row(model, itr, cost):
+    """The train_log.jsonl line of iteration itr: the loss, and with conf['grad_clip_norm'] / conf['grad_norm_log'] on the last
+    step's gradient norm (of the averaged gradient, before clipping) and clip scale.  Reading them synchronises, like float(cost)."""
+    row = {'itr': itr, 'training_loss': cost}
+    if model.graph.clip_norm is not None:
+        norm, scale = model.graph.grad_norm().tolist()
+        row['grad_norm'], row['grad_clip_scale'] = norm, scale
+    return row
 
 
 def _event_writer(conf):
@@ -252,9 +264,12 @@ def main(argv=None):
             c = float(cost)
             if rank == 0:
                 print(str(itr) + ' ' + str(c))
-                log.write(json.dumps({'itr': itr, 'training_loss': c}) + '\n')
+                row = training_log_row(model, itr, c)
+                log.write(json.dumps(row) + '\n')
                 if events is not None:
-                    log_value(events, c, 'training_loss', itr)
+                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale'):
+                        if key in row:
+                            log_value(events, row[key], key, itr)
         if itr % VAL_INTERVAL == 0 and itr != 0:
             vc = float(model.forward(**val_data.next()))
             if rank == 0:

@@ -477,6 +477,41 @@ int mv3d_ema_step(int64_t count, void* shadow, const void* params, float one_min
  * Kernel label: swap_kernel. */
 int mv3d_swap_f32(int64_t count, void* a, void* b, void* stream);
 
+/* ---- global-norm gradient clipping (the tf.clip_by_global_norm step of a TF-1.x trainer, over ONE flat gradient buffer) ------
+ * n = ||g||_2 * pre_scale over `count` >= 1 floats; s = clip_norm / n where n > clip_norm, else 1; out[0] = n, out[1] = s, and
+ * slot 6 (MV3D_ADAM_GSCALE / MV3D_SGD_GSCALE) of each optimiser record given becomes pre_scale * s: the optimiser launch that
+ * follows on the same stream multiplies every gradient by it, so no gradient is rewritten.  g is only read and 16-byte aligned;
+ * out is 4-byte aligned (2 floats); state_a / state_b may each be NULL.  pre_scale (the 1 / world size of a data-parallel step)
+ * is finite and > 0; clip_norm is > 0, +INFINITY = measure only (s is then always 1).  The workspace is the caller's, at least
+ * mv3d_grad_clip_workspace_bytes(count) bytes (0 for count < 1; >= 8 * ceil(count / 16384)), 16-byte aligned: no global device
+ * state, no atomics.  MV3D_E_INVAL before any launch: count < 1; g, out or workspace NULL; g not 16-byte, out / state_a / state_b
+ * not 4-byte aligned; pre_scale or clip_norm out of range (NaN included).  MV3D_E_WORKSPACE: workspace too small or misaligned.
+ *
+ * Two launches.  grad_sumsq_kernel: a 4 B/element read stream; the buffer is cut into chunks of 16384 floats (256 threads x 16
+ * float4; fixed, whatever the device and the grid), a workgroup walks chunks with a grid stride and writes ONE double per chunk.
+ * grad_clip_final_kernel: one workgroup of 256 sums the chunk partials, thread 0 finishes.
+ *
+ * Order contract (the numpy twin graph.grad_clip_rule follows it; results are the same bits on every run and every grid):
+ *   - every element is converted to double and squared: exact, 24 x 24 bits fit in 53
+ *   - thread t of a chunk owns float4s t + 256 k, k = 0 .. 15, of that chunk and adds their squares to ONE double accumulator
+ *     that starts at 0, in the order k = 0 .. 15, components x, y, z, w; elements at or past `count` (the partial last chunk,
+ *     the count & 3 tail) count as 0
+ *   - the 256 accumulators: xor butterfly with offsets 32, 16 .. 1 inside each wave of 64, then ((w0 + w1) + w2) + w3
+ *   - final kernel: thread t adds the chunk sums t, t + 256, .. in index order to one double that starts at 0, then the same
+ *     workgroup sum gives S
+ *   - thread 0, fp32 and uncontracted but for the root: n = (float)sqrt(S) * pre_scale (sqrt in double, correctly rounded);
+ *     s = n > clip_norm ? clip_norm / n : 1.0f; state[6] = pre_scale * s
+ * Deliberate differences from tf.clip_by_global_norm:
+ *   - not TF's clip * min(1 / n, 1 / clip): a step that is not clipped multiplies by exactly pre_scale and so keeps the bits of
+ *     an unclipped step
+ *   - a NaN norm compares false: the scale stays 1, the NaNs stay visible in the loss and in out[0] (TF would spread them)
+ *   - an infinite norm gives scale 0 (the step is dropped)
+ *   - the sums are double: a gradient with entries of 1e30 has a finite norm where an fp32 sum of squares overflows
+ * Kernel labels: grad_sumsq_kernel, grad_clip_final_kernel. */
+size_t mv3d_grad_clip_workspace_bytes(int64_t count);
+int mv3d_grad_clip_scale(int64_t count, const void* g, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- gradient finalisation: the slab reductions of ALL filter gradients (+ their optimiser update) in one launch ------------
  * Replaces, on the recorded single-GPU step, the per-layer partial-filter reductions behind tf.gradients' Conv2DBackpropFilter
  * ops and the tf.train.AdamOptimizer ApplyAdam ops of every variable that is not an fc matrix (appearance_flow_model.py:77).
