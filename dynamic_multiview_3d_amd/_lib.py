@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MV3D_LIB") or os.path.join(HERE, "libmv3d_hip.so")   
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 ACT_BY_NAME = {None: ACT_NONE, 'none': ACT_NONE, 'lrelu': ACT_LRELU, 'relu': ACT_RELU, 'tanh': ACT_TANH}
 F32 = 0
+ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2      # MV3D_ACCUM_* (mv3d_grad_accumulate)
 
 
 class ConvGeom(C.Structure):
@@ -91,6 +92,8 @@ STATUS_FUNCS = {
     "mv3d_ema_step": [_i64, _vp, _vp, _f, _vp],
     "mv3d_swap_f32": [_i64, _vp, _vp, _vp],
     "mv3d_grad_clip_scale": [_i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mv3d_grad_clip_finish": [_i64, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mv3d_grad_accumulate": [_i64, _vp, _vp, _i, _vp, _vp, _f, _vp, _sz, _vp],
     "mv3d_grad_finalize_begin": [],
     "mv3d_grad_finalize_add": [_vp, _i64],
     "mv3d_grad_finalize_commit": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],

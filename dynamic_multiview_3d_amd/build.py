@@ -23,6 +23,7 @@ UNITS = {
     "elem.hip": ["-ffp-contract=off"],
     "ema.hip": ["-ffp-contract=off"],
     "grad_norm.hip": ["-ffp-contract=off"],
+    "grad_accum.hip": ["-ffp-contract=off"],
     "resampler.hip": ["-ffp-contract=off"],
     "process_image.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],

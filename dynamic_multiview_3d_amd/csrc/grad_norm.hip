@@ -8,17 +8,8 @@
 
 namespace mv3d {
 
-constexpr int GN_UNROLL = 16;                        // float4s a lane loads per chunk, all issued before the first use
-constexpr int GN_CHUNK4 = GN_UNROLL * SUM_THREADS;   // float4s per chunk
-constexpr int GN_CHUNK = 4 * GN_CHUNK4;              // floats per chunk (16384): fixed, whatever the device and the grid
-// The grid: one workgroup per chunk up to 8 per CU (256 CUs), beyond that the workgroups walk the chunks with a grid stride.  The
-// chunk sums do not depend on it.
-constexpr int GN_MAX_BLOCKS = 2048;
-
-__device__ __forceinline__ double sq(float x) {
-    const double d = (double)x;
-    return d * d;                                    // exact: 24 x 24 bits
-}
+// GN_UNROLL (float4s a lane loads per chunk, all issued before the first use), GN_CHUNK, GN_MAX_BLOCKS and sq(): sum_common.h, which
+// grad_accum.hip shares.
 
 // Pass 1, a pure 4 B/element read stream, no LDS traffic but the four wave sums.  A lane has GN_UNROLL 16-byte loads (256 B) in
 // flight, a workgroup 64 KiB.  part[c] = the chunk's sum of squares, in the header's order.
@@ -84,8 +75,6 @@ __global__ __launch_bounds__(SUM_THREADS) void grad_clip_final_kernel(int64_t nc
     }
 }
 
-static inline int64_t gn_chunks(int64_t count) { return cdiv64(count, GN_CHUNK); }
-
 }  // namespace mv3d
 
 using namespace mv3d;
@@ -99,12 +88,11 @@ size_t mv3d_grad_clip_workspace_bytes(int64_t count) {
     return (size_t)cdiv64(gn_chunks(count) * (int64_t)sizeof(double), 256) * 256;
 }
 
-int mv3d_grad_clip_scale(int64_t count, const void* g, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "mv3d_grad_clip_scale";
+// The checks mv3d_grad_clip_scale and mv3d_grad_clip_finish share (everything but g).
+static int clip_args(const char* fn, int64_t count, float pre_scale, float clip_norm, const void* out, const void* state_a,
+                     const void* state_b, const void* workspace, size_t workspace_bytes) {
     if (count < 1) return fail(MV3D_E_INVAL, "%s: count (%lld) must be at least 1", fn, (long long)count);
-    if (!g || !out || !workspace) return fail(MV3D_E_INVAL, "%s: g, out or workspace is null", fn);
-    if ((uintptr_t)g & 15) return fail(MV3D_E_INVAL, "%s: g must be 16-byte aligned", fn);
+    if (!out || !workspace) return fail(MV3D_E_INVAL, "%s: out or workspace is null", fn);
     if (((uintptr_t)out | (uintptr_t)state_a | (uintptr_t)state_b) & 3)
         return fail(MV3D_E_INVAL, "%s: out, state_a or state_b not 4-byte aligned", fn);
     if (!std::isfinite(pre_scale) || !(pre_scale > 0.f))
@@ -114,18 +102,42 @@ int mv3d_grad_clip_scale(int64_t count, const void* g, float pre_scale, float cl
     const size_t need = mv3d_grad_clip_workspace_bytes(count);
     if (workspace_bytes < need) return fail(MV3D_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
     if ((uintptr_t)workspace & 15) return fail(MV3D_E_WORKSPACE, "%s: workspace not 16-byte aligned", fn);
+    return MV3D_OK;
+}
+
+static int clip_final(int64_t count, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b, const void* workspace,
+                      void* stream) {
     const int64_t nchunk = gn_chunks(count);
-    const int blocks = (int)std::min<int64_t>(nchunk, GN_MAX_BLOCKS);
-    double* part = (double*)workspace;
-    int rc = dispatch(stream, OpInfo{"grad_sumsq_kernel", 2.0 * count, 4.0 * count}, [=](hipStream_t s) {
-        grad_sumsq_kernel<<<blocks, SUM_THREADS, 0, s>>>(count, (const float*)g, part);
-        return launched("grad_sumsq_kernel");
-    });
-    if (rc != MV3D_OK) return rc;
+    const double* part = (const double*)workspace;
     return dispatch(stream, OpInfo{"grad_clip_final_kernel", 0.0, 8.0 * nchunk}, [=](hipStream_t s) {
         grad_clip_final_kernel<<<1, SUM_THREADS, 0, s>>>(nchunk, part, pre_scale, clip_norm, (float*)out, (float*)state_a, (float*)state_b);
         return launched("grad_clip_final_kernel");
     });
+}
+
+int mv3d_grad_clip_scale(int64_t count, const void* g, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "mv3d_grad_clip_scale";
+    if (count >= 1 && !g) return fail(MV3D_E_INVAL, "%s: g is null", fn);
+    if (count >= 1 && ((uintptr_t)g & 15)) return fail(MV3D_E_INVAL, "%s: g must be 16-byte aligned", fn);
+    int rc = clip_args(fn, count, pre_scale, clip_norm, out, state_a, state_b, workspace, workspace_bytes);
+    if (rc != MV3D_OK) return rc;
+    const int64_t nchunk = gn_chunks(count);
+    const int blocks = (int)std::min<int64_t>(nchunk, GN_MAX_BLOCKS);
+    double* part = (double*)workspace;
+    rc = dispatch(stream, OpInfo{"grad_sumsq_kernel", 2.0 * count, 4.0 * count}, [=](hipStream_t s) {
+        grad_sumsq_kernel<<<blocks, SUM_THREADS, 0, s>>>(count, (const float*)g, part);
+        return launched("grad_sumsq_kernel");
+    });
+    if (rc != MV3D_OK) return rc;
+    return clip_final(count, pre_scale, clip_norm, out, state_a, state_b, workspace, stream);
+}
+
+int mv3d_grad_clip_finish(int64_t count, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
+                          const void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = clip_args("mv3d_grad_clip_finish", count, pre_scale, clip_norm, out, state_a, state_b, workspace, workspace_bytes);
+    if (rc != MV3D_OK) return rc;
+    return clip_final(count, pre_scale, clip_norm, out, state_a, state_b, workspace, stream);
 }
 
 }  // extern "C"

@@ -99,6 +99,28 @@ def grad_clip_rule(g, pre_scale, clip_norm):
         return np.float32(n), np.float32(s), np.float32(pre * s)
 
 
+def grad_accum_rule(grads_list, losses=None):
+    """numpy twin of mv3d_grad_accumulate over one cycle: (sum, loss mean).  sum = ((g1 + g2) + g3) .. in float32, left to right
+    -- what MV3D_ACCUM_STORE, then ADD .., then FINISH leave in the gradient buffer, bit for bit (the optimiser multiplies it by
+    float32(1 / (world size * N)) through its gradient-scale slot); loss mean = ((l1 + l2) + ..) * float32(1 / N), or None
+    without losses."""
+    gs = [np.asarray(g, np.float32) for g in grads_list]
+    if not gs:
+        raise ValueError("grad_accum_rule: no gradients")
+    with np.errstate(over='ignore', invalid='ignore'):
+        total = gs[0].copy()
+        for g in gs[1:]:
+            total = total + g
+        if losses is None:
+            return total, None
+        if len(losses) != len(gs):
+            raise ValueError("grad_accum_rule: %d losses for %d gradients" % (len(losses), len(gs)))
+        mean = np.float32(losses[0])
+        for l in losses[1:]:
+            mean = np.float32(mean + np.float32(l))
+        return total, np.float32(mean * np.float32(1.0 / len(gs)))
+
+
 def current_graph():
     if not _current:
         raise RuntimeError("no Graph is active: build models inside `with Graph(...) as g:`")
@@ -699,6 +721,13 @@ class Graph:
         self.clip_norm = None
         self.clip_buf = None            # device [norm, scale] of the last step
         self._clip_ws, self._clip_ws_bytes = None, 0
+        # gradient accumulation (enable_grad_accum): accum_steps micro-batches per optimiser update, their gradients summed by
+        # mv3d_grad_accumulate into grad_sum (a second flat buffer) and, by the last micro-step, back into grads
+        self.accum_steps = 0            # N >= 2, or 0 = off
+        self.grad_sum = None
+        self.micro_step = 0             # position in the cycle, 0 .. N - 1
+        self._accum_loss = None         # two floats: the running loss sum of the current cycle and the mean of the last completed one
+        self._accum_slot, self._accum_done = 0, 1
 
     OPTIMIZERS = ('adam', 'momentum', 'sgd')
 
@@ -781,6 +810,8 @@ class Graph:
             self.ema = self.params.clone()
         if self.clip_norm is not None:
             self._alloc_grad_clip()
+        if self.accum_steps:
+            self._alloc_grad_accum()
         # optimiser slots: Adam m and v, one momentum accumulator, or none (gradient descent)
         if self.optimizer not in self.OPTIMIZERS:
             raise ValueError("unknown optimizer %r (have %s)" % (self.optimizer, ', '.join(self.OPTIMIZERS)))
@@ -1103,8 +1134,9 @@ class Graph:
         self.plan_bwd_fused = None
         self._fused_vars = []
         self._fused_nodes = []
-        # (not with gradient clipping: the fused kernels never write the fc gradients to memory, and the norm needs all of them)
-        if self.fuse_fc_adam and self.clip_norm is None and self.lr is not None and any(isinstance(n, LinearNode) for n in self.nodes):
+        # (not with gradient clipping: the fused kernels never write the fc gradients to memory, and the norm needs all of them;
+        # not with gradient accumulation either: the sum needs them, and only the last micro-step updates)
+        if self.fuse_fc_adam and self.clip_norm is None and not self.accum_steps and self.lr is not None and any(isinstance(n, LinearNode) for n in self.nodes):
             for t, (gw, gm) in zip(self.tensors, flags_after_forward):
                 t.grad_written, t.grad_masked = gw, gm
             plan = lib.plan_create()
@@ -1293,7 +1325,7 @@ class Graph:
         if self.clip_norm is None:
             raise RuntimeError("clip_gradients: gradient clipping is off (Graph.enable_grad_clip / conf['grad_clip_norm'])")
         self._settle()
-        self.lib.grad_clip_scale(self.flat_size, self.grads.data_ptr(), float(np.float32(1.0 / self.world_size)), self.clip_norm,
+        self.lib.grad_clip_scale(self.flat_size, self.grads.data_ptr(), self._grad_pre_scale(), self.clip_norm,
                                  self.clip_buf.data_ptr(), self.opt_state.data_ptr(), self.opt_state.data_ptr() + 32,
                                  self._clip_ws.data_ptr(), self._clip_ws_bytes, self._stream_ptr())
 
@@ -1317,6 +1349,87 @@ class Graph:
             self.run_backward()
         self.clip_gradients()
         self.apply_optimizer()
+
+    # ---------------------------------------------------------------- gradient accumulation
+    def enable_grad_accum(self, steps):
+        """One optimiser update out of `steps` train_step() calls (micro-steps), each a forward and a plain reverse pass on its own
+        micro-batch: call before compile().  None, 0 or 1 leave the switch off (nothing allocated, the same plans and launches); a
+        bool, a non-integer or a negative value raises ValueError.  The network has no batch statistics and every loss is a mean
+        over the batch, so N micro-batches of B give the gradient of one batch of N * B, up to rounding."""
+        if steps is None:
+            return
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+            raise ValueError("enable_grad_accum: steps must be an integer >= 2 (or None / 0 / 1 for off), got %r" % (steps,))
+        if steps < 2:
+            return
+        if self.plan_fwd is not None:
+            raise RuntimeError("enable_grad_accum: call it before compile()")
+        self.accum_steps = int(steps)
+        if self.finalized and self.grad_sum is None:
+            self._alloc_grad_accum()
+
+    def _alloc_grad_accum(self):
+        self.grad_sum = torch.zeros(self.flat_size, dtype=torch.float32, device=self.device)
+        self._accum_loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def _grad_pre_scale(self):
+        """float32(1 / (world size * micro-steps per update)): what turns the summed gradient buffer into the mean."""
+        return float(np.float32(1.0 / (self.world_size * max(self.accum_steps, 1))))
+
+    def accum_loss(self):
+        """The device scalar ((l1 + l2) + ..) * float32(1 / N) over the micro-batches of the last completed cycle (0 before the
+        first).  Converting it to a Python float is the caller's synchronisation."""
+        if not self.accum_steps:
+            raise RuntimeError("accum_loss: gradient accumulation is off (Graph.enable_grad_accum / conf['grad_accum_steps'])")
+        return self._accum_loss[self._accum_done]
+
+    def accumulate_gradients(self, fused_norm=False):
+        """mv3d_grad_accumulate on the main stream behind the reverse pass of micro-step `micro_step`: STORE into grad_sum on the
+        first, ADD on those between, FINISH on the last -- which writes the sum into grads, so that everything behind it reads
+        the flat gradient buffer as ever.  The loss scalar rides along.  fused_norm (last micro-step only): FINISH also writes
+        the chunk sums of squares of what it stored into the clipping workspace, for mv3d_grad_clip_finish."""
+        if not self.accum_steps:
+            raise RuntimeError("accumulate_gradients: gradient accumulation is off (Graph.enable_grad_accum / conf['grad_accum_steps'])")
+        self._settle()
+        n, k = self.accum_steps, self.micro_step
+        mode = _lib.ACCUM_STORE if k == 0 else (_lib.ACCUM_FINISH if k == n - 1 else _lib.ACCUM_ADD)
+        if fused_norm and (mode != _lib.ACCUM_FINISH or self.clip_norm is None):
+            raise RuntimeError("accumulate_gradients: fused_norm needs the last micro-step and gradient clipping")
+        self.lib.grad_accumulate(self.flat_size, self.grad_sum.data_ptr(), self.grads.data_ptr(), mode, self.loss_buf.data_ptr(),
+                                 self._accum_loss.data_ptr() + 4 * self._accum_slot, float(np.float32(1.0 / n)),
+                                 self._clip_ws.data_ptr() if fused_norm else None, self._clip_ws_bytes if fused_norm else 0,
+                                 self._stream_ptr())
+
+    def run_micro_step(self, data_parallel=None):
+        """Reverse pass and what follows it in one micro-step of an accumulation cycle (train_step() has run the forward pass).
+        Micro-steps 1 .. N - 1: the plain reverse pass, then STORE or ADD; no optimiser, no EMA, no beta-power advance, no
+        communication -- parameters and slots keep their bits.  Micro-step N: the plain reverse pass and FINISH; data parallel
+        (default: world size > 1) ONE all-reduce over the whole buffer, N times less communication than a step per micro-batch;
+        with clipping the norm of the mean gradient, pre_scale = float32(1 / (world size * N)) -- single GPU
+        mv3d_grad_clip_finish over the partials FINISH wrote, data parallel the ordinary mv3d_grad_clip_scale behind the
+        all-reduce (which changes the buffer); then apply_optimizer(), once per update, on every rank over the whole buffer:
+        complete slots and bit-identical weights on every rank, as in the clipped schedule."""
+        dp = self.world_size > 1 if data_parallel is None else data_parallel
+        self.run_backward()
+        last = self.micro_step == self.accum_steps - 1
+        fused_norm = last and self.clip_norm is not None and not dp
+        self.accumulate_gradients(fused_norm=fused_norm)
+        if not last:
+            self.micro_step += 1
+            return
+        if dp:
+            # allreduce_grads() without its world-size test (it skips at world size 1): data_parallel=True runs the exchange
+            # through the communicator whatever the world size, which is how a one-GPU test covers this schedule
+            self.comm.allreduce_sum_(self.grads, 0, self.flat_size, self._stream_ptr())
+        if fused_norm:
+            self.lib.grad_clip_finish(self.flat_size, self._grad_pre_scale(), self.clip_norm, self.clip_buf.data_ptr(),
+                                      self.opt_state.data_ptr(), self.opt_state.data_ptr() + 32, self._clip_ws.data_ptr(),
+                                      self._clip_ws_bytes, self._stream_ptr())
+        elif self.clip_norm is not None:
+            self.clip_gradients()
+        self.apply_optimizer()
+        self.micro_step = 0
+        self._accum_done, self._accum_slot = self._accum_slot, self._accum_done
 
     def _finalize_commit(self):
         """Close the open mv3d_grad_finalize collection: one launch on the filter-gradient stream that sums the collected layers'
@@ -1463,14 +1576,14 @@ class Graph:
 
     def upload_optimizer_state(self):
         """The device optimiser state: Adam's lr, betas, epsilon and the two beta powers, or Momentum / GD's lr, momentum and
-        Nesterov flag; then the gradient scale (1 / world size)."""
+        Nesterov flag; then the gradient scale (1 / world size; with gradient accumulation 1 / (world size * micro-steps))."""
         if self.opt_state is None or self.lr is None:
             return
         if self.optimizer == 'adam':
             vals = [self.lr, self.beta1, self.beta2, self.eps, self.beta1_power, self.beta2_power]
         else:
             vals = [self.lr, self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0, 0.0, 0.0]
-        vals = np.array(vals + [1.0 / self.world_size, 0.0], np.float32)
+        vals = np.array(vals + [1.0 / (self.world_size * max(self.accum_steps, 1)), 0.0], np.float32)
         self._settle()
         self.opt_state.copy_(torch.from_numpy(np.concatenate([vals, vals])))
 
@@ -1686,10 +1799,14 @@ class Graph:
                 self.ema_updates += 1
 
     def train_step(self):
-        """forward + loss + reverse pass + (all-reduce) + optimiser (+ EMA of the weights); returns the device loss scalar."""
+        """forward + loss + reverse pass + (all-reduce) + optimiser (+ EMA of the weights); returns the device loss scalar.  With
+        gradient accumulation one micro-step (run_micro_step): every accum_steps-th call updates, and the scalar returned is the
+        micro-batch's loss (accum_loss() is the cycle's mean)."""
         self._check_not_swapped('train_step')
         self.run_forward()
-        if self.clip_norm is not None:
+        if self.accum_steps:
+            self.run_micro_step()
+        elif self.clip_norm is not None:
             self.run_backward_clipped()
         elif self.world_size > 1:
             self.run_backward_overlapped(with_adam=True)
@@ -1713,6 +1830,9 @@ class Graph:
             self.variables[k].value().copy_(torch.as_tensor(np.asarray(a, dtype=np.float32)).reshape(self.variables[k].shape))
 
     def get_gradients(self):
+        """One host array per variable with a gradient, as the flat gradient buffer holds it.  With gradient accumulation, after
+        an update that is the UNSCALED sum over the cycle's micro-batches (the optimiser applied float32(1 / (world size * N))
+        through its gradient-scale slot); in the middle of a cycle it is the last micro-batch's own gradient."""
         self._settle()
         return OrderedDict((k, v.grad_value().detach().cpu().numpy().copy()) for k, v in self.variables.items() if v.has_grad)
 
@@ -1750,8 +1870,12 @@ class Graph:
         """TF-Saver-style names: <var> and the active optimiser's slots -- <var>/Adam, <var>/Adam_1, beta1_power, beta2_power
         (Adam), <var>/Momentum (Momentum), nothing else (GD) -- (train.py:70-71 saves GLOBAL_VARIABLES).  With EMA on also
         <var>/ExponentialMovingAverage for EVERY variable (TF's shadow variables) and the update counter
-        ExponentialMovingAverage/num_updates; every data-parallel rank holds the complete shadows."""
+        ExponentialMovingAverage/num_updates; every data-parallel rank holds the complete shadows.  With gradient accumulation
+        it raises RuntimeError in the middle of a cycle: the partial gradient sum is not part of a checkpoint."""
         self._check_not_swapped('state_dict')
+        if self.accum_steps and self.micro_step:
+            raise RuntimeError("state_dict() in the middle of an accumulation cycle (micro-step %d of %d): the partial gradient sum is "
+                               "not checkpointed; save at an update boundary" % (self.micro_step, self.accum_steps))
         self._settle()
         if self.world_size > 1 and getattr(self, '_slots_sharded', False):
             raise RuntimeError("sharded data-parallel step: this rank holds 1/%d of the optimiser slots; call "
@@ -1821,6 +1945,7 @@ class Graph:
             else:
                 self.ema.copy_(self.params)
                 self.ema_updates = 0
+        self.micro_step = 0             # an accumulation cycle starts afresh on the restored weights
         self.upload_optimizer_state()
 
 

@@ -14,6 +14,7 @@ import torch
 from . import tf_checkpoint
 from .graph import Graph, ema_one_minus_decay, ema_rule      # noqa: F401  (the numpy twins of mv3d_ema_step are part of this module's interface)
 from .graph import grad_clip_rule                            # noqa: F401  (... and the twin of mv3d_grad_clip_scale)
+from .graph import grad_accum_rule                           # noqa: F401  (... and the twin of mv3d_grad_accumulate)
 
 
 class Saver:
@@ -135,6 +136,19 @@ def grad_clip_from_conf(conf):
     if not math.isfinite(c) or not c > 0.0 or not 0.0 < c32 < math.inf:
         raise ValueError("conf['grad_clip_norm'] must be finite (as a float32) and > 0 (or 0 / None for off), got %r" % (conf['grad_clip_norm'],))
     return c
+
+
+def grad_accum_from_conf(conf):
+    """The N Graph.enable_grad_accum takes, or None for off (the graph then allocates, records and launches exactly what it did
+    without the key).  conf['grad_accum_steps'] = N, an integer >= 2, makes one optimiser update out of N train steps
+    (micro-batches of conf['batch_size'] each); absent, None, 0 or 1 is off.  A bool, a non-integer or a negative value raises
+    ValueError, before any device work."""
+    n = conf.get('grad_accum_steps')
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError("conf['grad_accum_steps'] must be an integer >= 2 (or None / 0 / 1 for off), got %r" % (n,))
+    return int(n) if n >= 2 else None
 
 
 def ssim_weight_from_conf(conf):
@@ -299,6 +313,7 @@ class ModelBase(object):
         self._check_conf()
         ema_from_conf(self.conf)        # a bad conf['ema_decay'] raises here, before any device work
         grad_clip_from_conf(self.conf)  # ... and a bad conf['grad_clip_norm']
+        grad_accum_from_conf(self.conf)  # ... and a bad conf['grad_accum_steps']
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 
@@ -313,6 +328,9 @@ class ModelBase(object):
         clip = grad_clip_from_conf(self.conf)
         if clip is not None and build_loss:     # a property of the train step: a model without a loss has no gradient
             self.graph.enable_grad_clip(clip)
+        accum = grad_accum_from_conf(self.conf)
+        if accum is not None and build_loss:    # likewise a property of the train step
+            self.graph.enable_grad_accum(accum)
         self.graph.compile()
 
     def ema_weights(self):
@@ -330,7 +348,8 @@ class ModelBase(object):
 
     def train_step(self, **feeds):
         """One sess.run([model.loss, model.train_op], {train_cond: 1}); returns the loss as a
-        0-d device tensor (call float() on it to synchronise)."""
+        0-d device tensor (call float() on it to synchronise).  With conf['grad_accum_steps'] = N one micro-step: the N-th call
+        in a row updates the weights (Graph.run_micro_step)."""
         if self.graph.loss_expr is None:
             raise RuntimeError("model was built with build_loss=False")
         self.feed(**feeds)

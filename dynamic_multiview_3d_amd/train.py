@@ -22,6 +22,10 @@ With conf['ema_decay'] the checkpoints carry the averaged weights (<var>/Exponen
 run on them; --raw_weights opts out.  The periodic val_loss during training stays on the raw weights.
 With conf['grad_clip_norm'] (or conf['grad_norm_log']) the lines written every 10th iteration also carry `grad_norm` and
 `grad_clip_scale` of that step, in the JSON-lines log and, with --event_log, as scalars.
+With conf['grad_accum_steps'] = N an iteration is one optimiser update: N batches of conf['batch_size'] drawn from the input and N
+model.train_step() calls (micro-steps).  The logged `training_loss` is then the mean over the update's micro-batches, `grad_norm`
+and `grad_clip_scale` belong to the averaged accumulated gradient, the printed time per iteration is per update, and checkpoints
+are written at update boundaries only.
 """
 import argparse
 import importlib
@@ -119,6 +123,59 @@ def training_log_row(model, itr, cost):
         norm, scale = model.graph.grad_norm().tolist()
         row['grad_norm'], row['grad_clip_scale'] = norm, scale
     return row
+
+
+def train_iteration(model, train_data):
+    """One iteration of the training loop = one optimiser update; returns the device loss scalar to log.  Without gradient
+    accumulation one batch and one model.train_step(); with conf['grad_accum_steps'] = N, N batches and N micro-steps, and the loss
+    is Graph.accum_loss(), the mean over them."""
+    n = model.graph.accum_steps
+    if not n:
+        return model.train_step(**train_data.next())
+    for _ in range(n):
+        model.train_step(**train_data.next())
+    return model.graph.accum_loss()
+
+
+def train_loop(model, conf, train_data, val_data, saver, itr_0=0, rank=0, log=None, events=None):
+    """Iterations itr_0 .. conf['num_iterations'] inclusive (train.py:117): a log line every 10th, validation every 500th, a
+    checkpoint every 10 000th.  log (a text file) and events (a summary.FileWriter or None) are rank 0's."""
+    starttime = time.time()
+    t_iter = []
+    for itr in range(itr_0, conf['num_iterations'] + 1, 1):         # inclusive, train.py:117
+        t_startiter = time.time()
+        cost = train_iteration(model, train_data)
+        if itr % 10 == 0:
+            c = float(cost)
+            if rank == 0:
+                print(str(itr) + ' ' + str(c))
+                row = training_log_row(model, itr, c)
+                log.write(json.dumps(row) + '\n')
+                if events is not None:
+                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale'):
+                        if key in row:
+                            log_value(events, row[key], key, itr)
+        if itr % VAL_INTERVAL == 0 and itr != 0:
+            vc = float(model.forward(**val_data.next()))
+            if rank == 0:
+                log.write(json.dumps({'itr': itr, 'val_loss': vc}) + '\n')
+                if events is not None:
+                    log_value(events, vc, 'val_loss', itr)
+        if itr % SAVE_INTERVAL == 0 and itr != 0:
+            model.graph.gather_optimizer_state()        # collective: the sharded optimiser's slots, complete on every rank
+            if rank == 0:
+                print('Saving model to' + conf['output_dir'])
+                saver.save(None, conf['output_dir'] + '/model' + str(itr))
+        t_iter.append(time.time() - t_startiter)
+        if itr % 100 == 1 and rank == 0:
+            if model.graph.device.type == 'cuda':
+                torch.cuda.synchronize()
+            avg_t_iter = (time.time() - starttime) / (itr - itr_0 + 1)
+            print('time per iteration: {0}'.format(avg_t_iter))
+            print('expected for complete training: {0}h '.format(avg_t_iter / 3600 * conf['num_iterations']))
+            log.flush()
+            if events is not None:
+                events.flush()
 
 
 def _event_writer(conf):
@@ -255,41 +312,7 @@ def main(argv=None):
     gc.collect()
     gc.freeze()
 
-    starttime = time.time()
-    t_iter = []
-    for itr in range(itr_0, conf['num_iterations'] + 1, 1):         # inclusive, train.py:117
-        t_startiter = time.time()
-        cost = model.train_step(**train_data.next())
-        if itr % 10 == 0:
-            c = float(cost)
-            if rank == 0:
-                print(str(itr) + ' ' + str(c))
-                row = training_log_row(model, itr, c)
-                log.write(json.dumps(row) + '\n')
-                if events is not None:
-                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale'):
-                        if key in row:
-                            log_value(events, row[key], key, itr)
-        if itr % VAL_INTERVAL == 0 and itr != 0:
-            vc = float(model.forward(**val_data.next()))
-            if rank == 0:
-                log.write(json.dumps({'itr': itr, 'val_loss': vc}) + '\n')
-                if events is not None:
-                    log_value(events, vc, 'val_loss', itr)
-        if itr % SAVE_INTERVAL == 0 and itr != 0:
-            model.graph.gather_optimizer_state()        # collective: the sharded optimiser's slots, complete on every rank
-            if rank == 0:
-                print('Saving model to' + conf['output_dir'])
-                saver.save(None, conf['output_dir'] + '/model' + str(itr))
-        t_iter.append(time.time() - t_startiter)
-        if itr % 100 == 1 and rank == 0:
-            torch.cuda.synchronize()
-            avg_t_iter = (time.time() - starttime) / (itr - itr_0 + 1)
-            print('time per iteration: {0}'.format(avg_t_iter))
-            print('expected for complete training: {0}h '.format(avg_t_iter / 3600 * conf['num_iterations']))
-            log.flush()
-            if events is not None:
-                events.flush()
+    train_loop(model, conf, train_data, val_data, saver, itr_0, rank, log if rank == 0 else None, events)
     model.graph.gather_optimizer_state()
     if rank == 0:
         print('Saving model.')

@@ -511,6 +511,43 @@ int mv3d_swap_f32(int64_t count, void* a, void* b, void* stream);
 size_t mv3d_grad_clip_workspace_bytes(int64_t count);
 int mv3d_grad_clip_scale(int64_t count, const void* g, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* Pass 2 of mv3d_grad_clip_scale on its own: the grad_clip_final_kernel launch over chunk partials that are already in `workspace`
+ * (written by mv3d_grad_clip_scale's first launch or by mv3d_grad_accumulate in MV3D_ACCUM_FINISH mode with sumsq_part; the
+ * workspace is only read).  Same results, same order, same checks as mv3d_grad_clip_scale, g apart.  Kernel label:
+ * grad_clip_final_kernel. */
+int mv3d_grad_clip_finish(int64_t count, float pre_scale, float clip_norm, void* out, void* state_a, void* state_b,
+                          const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- gradient accumulation: N micro-batches' gradients summed over ONE flat gradient buffer, one optimiser update behind them ---
+ * `sum` and `g` hold `count` >= 1 floats each, are 16-byte aligned and do not overlap.  One launch per micro-batch, on the stream
+ * of the reverse pass that wrote g:
+ *   MV3D_ACCUM_STORE   sum[i] = g[i]             the first micro-batch: sum is not read and needs no memset; 8 B/element
+ *   MV3D_ACCUM_ADD     sum[i] = sum[i] + g[i]    12 B/element
+ *   MV3D_ACCUM_FINISH  g[i]   = sum[i] + g[i]    the last micro-batch, written into G: sum is only read; 12 B/element
+ * STORE and ADD leave g as it is.  Because FINISH writes into g, the norm and every optimiser kernel behind it read the flat
+ * gradient buffer as ever; the 1 / N of the mean goes into the gradient-scale slot of the optimiser records (slot 6), which
+ * mv3d_grad_clip_scale / mv3d_grad_clip_finish write through their pre_scale.  The sum is ((g1 + g2) + g3) .., one fp32 addition
+ * per element and launch, uncontracted; one writer per element, no atomics, no global device state: the same bits on every run
+ * and every grid.  graph.grad_accum_rule is the numpy twin.
+ *
+ * The loss rides along: `loss` and `loss_sum` are one float each (4-byte aligned), both given or both NULL.  STORE: loss_sum =
+ * loss; ADD: loss_sum = loss_sum + loss; FINISH: loss_sum = (loss_sum + loss) * loss_scale (the mean for loss_scale = 1 / N;
+ * loss_scale is read by FINISH only).  One thread of the launch does it.
+ *
+ * sumsq_part != NULL (FINISH only; at least mv3d_grad_clip_workspace_bytes(count) bytes, 16-byte aligned): the launch also writes
+ * one double per chunk of 16384 floats, the sum of squares of the values it STORED into g, by the order contract of
+ * grad_sumsq_kernel above -- the same chunking, thread t owns float4s t + 256 k and adds their squares to one double in the
+ * order k = 0 .. 15, x, y, z, w, elements at or past `count` count as 0, then the workgroup sum.  mv3d_grad_clip_finish on that
+ * workspace then gives the bits mv3d_grad_clip_scale gives on the stored buffer, and the norm's 4 B/element read pass is saved.
+ * (The loads of a chunk are issued in two rounds of 8 float4s per lane and buffer; the order of the additions does not depend
+ * on it.)
+ * MV3D_E_INVAL before any launch: count < 1; sum or g NULL, not 16-byte aligned, or overlapping; an unknown mode; one of loss /
+ * loss_sum without the other, or not 4-byte aligned; sumsq_part outside FINISH.  MV3D_E_WORKSPACE: sumsq_part too small or
+ * misaligned.
+ * Kernel labels: grad_accum_store_kernel, grad_accum_add_kernel, grad_accum_finish_kernel, grad_accum_finish_sumsq_kernel. */
+enum { MV3D_ACCUM_STORE = 0, MV3D_ACCUM_ADD = 1, MV3D_ACCUM_FINISH = 2 };
+int mv3d_grad_accumulate(int64_t count, void* sum, void* g, int mode, const void* loss, void* loss_sum, float loss_scale,
+                         void* sumsq_part, size_t sumsq_bytes, void* stream);
 
 /* ---- gradient finalisation: the slab reductions of ALL filter gradients (+ their optimiser update) in one launch ------------
  * Replaces, on the recorded single-GPU step, the per-layer partial-filter reductions behind tf.gradients' Conv2DBackpropFilter
