@@ -13,6 +13,7 @@ ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 ACT_BY_NAME = {None: ACT_NONE, 'none': ACT_NONE, 'lrelu': ACT_LRELU, 'relu': ACT_RELU, 'tanh': ACT_TANH}
 F32 = 0
 ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2      # MV3D_ACCUM_* (mv3d_grad_accumulate)
+AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE, AUG_CONTRAST = 1, 2, 4, 8      # MV3D_AUG_* (mv3d_color_augment)
 
 
 class ConvGeom(C.Structure):
@@ -81,6 +82,7 @@ STATUS_FUNCS = {
     "mv3d_tfrecord_read": [_vp, _i, _i, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(C.c_int)],
     "mv3d_u8_to_unit_f32": [_i64, _vp, _vp, _vp],
     "mv3d_u8_process_image": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    "mv3d_color_augment": [C.POINTER(_vp), _i, _i, _i, _i, _vp, C.c_uint, _vp, _sz, _vp],
     "mv3d_fill": [_vp, _i64, _f, _vp],
     "mv3d_adam_step": [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _vp],
     "mv3d_adam_step_dev": [_i64, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64), _vp],
@@ -140,6 +142,7 @@ OTHER_FUNCS = {
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_multiscale_warp_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "mv3d_grad_clip_workspace_bytes": (_sz, [_i64]),
+    "mv3d_color_augment_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_crc32c": (C.c_uint32, [_vp, _sz]),
     "mv3d_set_diagnostics": (C.c_int, [_i]),
     "mv3d_set_wgrad_cus": (C.c_int, [_i]),

@@ -314,6 +314,8 @@ class ModelBase(object):
         ema_from_conf(self.conf)        # a bad conf['ema_decay'] raises here, before any device work
         grad_clip_from_conf(self.conf)  # ... and a bad conf['grad_clip_norm']
         grad_accum_from_conf(self.conf)  # ... and a bad conf['grad_accum_steps']
+        from .augment import augment_from_conf
+        augment_from_conf(self.conf)     # ... and a bad conf['augment_*'] (the input path's colour stage: augment.py)
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 

@@ -329,7 +329,11 @@ class TFRecordInput:
     """Batches for a model: `next()` returns {graph input name: tensor on the model's device}.
 
     conf keys as in the reference: data_dir, train_val_split, batch_size, optional test_mode (no shuffle, all files); and
-    record_image_size (an int or (H, W)): the size of the images in the shards when it is not the model's (module docstring)."""
+    record_image_size (an int or (H, W)): the size of the images in the shards when it is not the model's (module docstring).
+    With conf['augment_*'] (augment.py) a training input (training=True and no test_mode) runs the colour stage on every batch: on
+    the device mv3d_color_augment in the input thread, on the reader's stream, behind the conversion kernels and before the batch's
+    event is recorded; with device='cpu' the numpy twin.  Validation, --evaluate and --visualize inputs never build it, and with
+    the keys absent nothing is built and the batches are the plain reader's."""
 
     def __init__(self, conf, input_shapes, training=True, device='cpu', seed=0, prefetch=4, verify=True, rank=0, world=1):
         self.files = split_files(conf, training)
@@ -346,6 +350,11 @@ class TFRecordInput:
         self.rng = np.random.default_rng(seed)
         self.device, self.verify = device, verify
         self.q = queue.Queue(maxsize=max(prefetch, 1))
+        self.augment = None
+        if training and 'test_mode' not in conf:
+            from . import augment
+            if augment.augment_from_conf(conf).enabled:      # a generator of its own: the shuffle order does not depend on the switch
+                self.augment = augment.ColorAugment(conf, input_shapes, device=device, rank=rank, ring=self.q.maxsize + 2)
         self._stop = False
         self._err = None
         self.thread = threading.Thread(target=self._produce, daemon=True)
@@ -420,6 +429,8 @@ class TFRecordInput:
                                 lib.u8_to_unit_f32(d.numel(), d.data_ptr(), f.data_ptr(), stream.cuda_stream)
                                 d = f
                             out[k] = d
+                        if self.augment is not None:
+                            self.augment.apply(out, stream)
                         ev = torch.cuda.Event()
                         ev.record(stream)
                     done[0] = ev
@@ -430,6 +441,8 @@ class TFRecordInput:
                             out[k] = torch.from_numpy(process_image(b.numpy(), self.spec[k][:2]))
                         else:
                             out[k] = b.clone() if kd else b.to(torch.float32) / np.float32(255.0)
+                    if self.augment is not None:
+                        self.augment.apply(out)
                 self.q.put((out, ev))
         except BaseException as e:       # surfaced by next()
             self._err = e

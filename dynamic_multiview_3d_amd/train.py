@@ -26,6 +26,10 @@ With conf['grad_accum_steps'] = N an iteration is one optimiser update: N batche
 model.train_step() calls (micro-steps).  The logged `training_loss` is then the mean over the update's micro-batches, `grad_norm`
 and `grad_clip_scale` belong to the averaged accumulated gradient, the printed time per iteration is per update, and checkpoints
 are written at update boundaries only.
+With conf['augment_brightness' / '_saturation' / '_hue' / '_contrast'] (augment.py) the training batches go through the colour stage,
+one colour map per sample over all of its colour views: the TFRecord reader runs it on its own stream, and synthetic training batches
+are handed out as augmented copies (the cycled pool stays pristine).  Validation, --evaluate and --visualize batches are never augmented;
+under data parallelism every rank draws from np.random.default_rng([augment_seed, rank]).
 """
 import argparse
 import importlib
@@ -267,6 +271,11 @@ def main(argv=None):
             print('no TFRecord shards at conf["data_dir"] = %r: training on synthetic batches' % (data_dir,))
         train_data = SyntheticData(model, seed=rank)
         val_data = SyntheticData(model, seed=10_000 + rank, pool=1)
+        from . import augment
+        if augment.augment_from_conf(conf).enabled and 'test_mode' not in conf:
+            # the pool is cycled: without this the same four batches would repeat forever.  Copies, so that the pool stays pristine
+            shapes = {k: tuple(t.shape) for k, t in model.graph.inputs.items()}
+            train_data = augment.AugmentedData(train_data, augment.ColorAugment(conf, shapes, device=model.graph.device, rank=rank))
 
     if FLAGS.visualize:                                               # train.py:80-92
         print('-------------------------------------------------------------------')

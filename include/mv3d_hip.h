@@ -96,6 +96,44 @@ int mv3d_u8_to_unit_f32(int64_t count, const void* src, void* dst, void* stream)
  * aligned; n*hs*ws*c or n*ho*wo*c >= 2^31 - 2^21 (32-bit indices).  Allocates nothing, keeps no state. */
 int mv3d_u8_process_image(const void* src, int n, int hs, int ws, int c, void* dst, int ho, int wo, void* stream);
 
+/* ---- colour augmentation: ONE pointwise colour map per sample, applied in place to all of the sample's colour views -----------
+ * The reference has no augmentation and TensorFlow was never run against this: the contract below is the project's own, and
+ * augment.color_augment_host is its numpy twin and the authority (input path: colour augmentation).
+ * images: a HOST array of `views` (1 .. 8) device pointers, each float32 [n, h, w, 3], 16-byte aligned, no two overlapping; read at
+ * call time and handed to the kernels by value.  params: device float32 [n, 4] = brightness delta db, saturation factor fs, hue
+ * delta dh, contrast factor fc of sample i.  stages: which stages run; a stage whose bit is clear is skipped, not run with a
+ * neutral value.  Every operation is an fp32 operation that rounds on its own (no contraction), every division is correctly
+ * rounded; clip(x) = x < 0 ? 0 : x > 1 ? 1 : x; max / min are a > b ? a : b / a < b ? a : b, left to right.  Per pixel (r, g, b):
+ *   BRIGHTNESS  c = c + db
+ *   SATURATION | HUE (one HSV round trip for both)
+ *               c = clip(c); v = max(r, g, b); mn = min(r, g, b); range = v - mn; s = v > 0 ? range / v : 0; norm = 1 / (6 * range)
+ *               h = r == v ? (g - b) * norm : g == v ? (b - r) * norm + 2.0f/6.0f : (r - g) * norm + 4.0f/6.0f
+ *               h = range <= 0 ? 0 : h;  h = h < 0 ? h + 1 : h
+ *               SATURATION: s = clip(s * fs)      HUE: h = h + dh      always: h = h - floor(h)
+ *               c = s * v; m = v - c; d = h * 6; k = min((int)d, 5); f = d - 2 * floor(d / 2); x = c * (1 - |f - 1|)
+ *               (r, g, b) = m + (c,x,0) (x,c,0) (0,c,x) (0,x,c) (x,0,c) (c,0,x) for k = 0 .. 5
+ *   CONTRAST    c = (c - pivot[ch]) * fc + pivot[ch]
+ *   always      c = clip(c)   (so a bicubic overshoot of the input is clipped whenever any stage runs)
+ * The device evaluates clip, max and min with the hardware's clamp / max3 / min3 and the hue branch as one (a - b) * norm + offset
+ * with the operands selected first: the same VALUES for every finite input (a zero may carry the other sign, which no later
+ * operation turns into a different non-zero value); NaN inputs are outside the contract.
+ * pivot[ch] of sample i: the mean of channel ch over ALL `views` images of the sample, of the input values, summed in double in a
+ * fixed order, divided by views * h * w in double and rounded to float once.  The order: an image is cut into chunks of 4096 pixels;
+ * thread t of 256 owns the pixel quads t + 256 k (k = 0 .. 3) of a chunk and adds their pixels in ascending order, one double per
+ * channel; the pixels behind the last whole quad (h * w & 3 of them) belong to the thread that would own that quad; the 256 sums
+ * are added as sum_common.h states (xor butterfly per wave, ((w0 + w1) + w2) + w3); the chunk sums are then added views ascending,
+ * chunks ascending within a view.  Nothing depends on the grid or the device; no atomics, no global state.
+ * Two launches with MV3D_AUG_CONTRAST (the chunk sums into `workspace`, 24 bytes per sample, view and chunk; then the map), one
+ * without it, which leaves the workspace untouched.
+ * MV3D_E_INVAL before any launch: images, params or workspace NULL, a NULL view; views outside 1 .. 8; n, h or w < 1; n*h*w*3 >=
+ * 2^31 - 2^21 (32-bit indices); stages 0 or with unknown bits; a view or params not 16-byte aligned; two views
+ * that are equal or overlap.  MV3D_E_WORKSPACE: workspace smaller than mv3d_color_augment_workspace_bytes() or not 16-byte aligned.
+ * Kernel labels: color_augment_sums_kernel, color_augment_apply_kernel. */
+enum { MV3D_AUG_BRIGHTNESS = 1, MV3D_AUG_SATURATION = 2, MV3D_AUG_HUE = 4, MV3D_AUG_CONTRAST = 8 };
+size_t mv3d_color_augment_workspace_bytes(int n, int views, int h, int w);
+int mv3d_color_augment(void* const* images, int views, int n, int h, int w, const void* params, unsigned stages,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* CRC-32C of a host buffer: the record checksum of the reference's TFRecord shards (multi_view_model/utils/read_tf_records.py:46-48
  * reads them through tf.TFRecordReader); used by dynamic_multiview_3d_amd/read_tf_records.py */
 uint32_t mv3d_crc32c(const void* data, size_t n);

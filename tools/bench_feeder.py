@@ -5,7 +5,8 @@ device-resident rate of bench.py (GPU box only): python tools/bench_feeder.py [s
 Without --record-size: AppearanceFlowModel, B = 64, 128 x 128 records of the model's own size.  With --record-size S: BASELINE
 config 5 -- MultiObjectAppFlow, fully_conv, 256 x 256, B = 32, 13 features -- fed from S x S records that the reader resizes on
 the device (conf['record_image_size'], mv3d_u8_process_image), and additionally the rate of the feeder alone (next() in a loop,
-nothing consuming the batches but a device synchronise at the end), which has to stay above the step's."""
+nothing consuming the batches but a device synchronise at the end), which has to stay above the step's.
+--augment sets the four conf['augment_*'] keys (augment.py): the reader then runs the colour stage on its stream on every batch."""
 import argparse
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +16,7 @@ from dynamic_multiview_3d_amd import read_tf_records as R
 ap = argparse.ArgumentParser()
 ap.add_argument('steps', nargs='?', type=int, default=40)
 ap.add_argument('--record-size', type=int, default=None, help='time config 5 (256 x 256 multi-object) fed from records of this size')
+ap.add_argument('--augment', action='store_true', help='switch on all four colour-augmentation stages of the reader')
 args = ap.parse_args()
 steps = args.steps
 tmp = tempfile.mkdtemp(prefix='mv3d_feed_')
@@ -40,6 +42,8 @@ else:
         s = {name: rng.integers(0, 256, (S, S, ch), dtype=np.uint8).tobytes() for name, ch in INPUTS}
         s['displacement'] = rng.uniform(-10, 10, 2).astype(np.float32)
         return s
+if args.augment:
+    conf.update({'augment_brightness': 0.3, 'augment_saturation': (0.3, 2), 'augment_hue': 0.5, 'augment_contrast': (0.4, 1.8)})
 for f in range(nfiles):
     with R.TFRecordWriter(os.path.join(tmp, '%d.tfrecords' % f)) as w:
         for i in range(per_file):
