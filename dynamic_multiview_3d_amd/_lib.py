@@ -13,6 +13,7 @@ ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 ACT_BY_NAME = {None: ACT_NONE, 'none': ACT_NONE, 'lrelu': ACT_LRELU, 'relu': ACT_RELU, 'tanh': ACT_TANH}
 F32 = 0
 ACCUM_STORE, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2      # MV3D_ACCUM_* (mv3d_grad_accumulate)
+DECAY_MAX_RANGES = 1024                             # MV3D_DECAY_MAX_RANGES (mv3d_weight_decay_step)
 AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE, AUG_CONTRAST = 1, 2, 4, 8      # MV3D_AUG_* (mv3d_color_augment)
 
 
@@ -93,6 +94,8 @@ STATUS_FUNCS = {
     "mv3d_fc_wgrad_sgd": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "mv3d_ema_step": [_i64, _vp, _vp, _f, _vp],
     "mv3d_swap_f32": [_i64, _vp, _vp, _vp],
+    "mv3d_opt_set_lr": [_vp, _f, _vp],
+    "mv3d_weight_decay_step": [_vp, _vp, _i64, _i64, _vp, _i, _f, _f, _vp],
     "mv3d_grad_clip_scale": [_i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
     "mv3d_grad_clip_finish": [_i64, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
     "mv3d_grad_accumulate": [_i64, _vp, _vp, _i, _vp, _vp, _f, _vp, _sz, _vp],

@@ -22,6 +22,7 @@ UNITS = {
     "fc.hip": [],
     "elem.hip": ["-ffp-contract=off"],
     "ema.hip": ["-ffp-contract=off"],
+    "weight_decay.hip": ["-ffp-contract=off"],
     "grad_norm.hip": ["-ffp-contract=off"],
     "grad_accum.hip": ["-ffp-contract=off"],
     "resampler.hip": ["-ffp-contract=off"],

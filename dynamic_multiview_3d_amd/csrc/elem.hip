@@ -419,6 +419,11 @@ __global__ void adam_advance_kernel(float* st) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st[4] = st[4] * st[1]; st[5] = st[5] * st[2]; }      // beta_power *= beta, in fp32 like TF's update op
 }
 
+// the scheduled learning rate of the NEXT update, written behind the last launch of this one that reads the record
+__global__ void opt_set_lr_kernel(float* st, float lr) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) st[MV3D_ADAM_LR] = lr;
+}
+
 // ---------------------------------------------------------------- GD / Momentum (TF ApplyGradientDescent / ApplyMomentum)
 // The counterparts of adam_kernel / adam_dev_kernel: MOM = false is plain gradient descent (loads p, g; stores p = 12 B/param),
 // MOM = true keeps the momentum slot a (20 B/param).  The arithmetic is common.h's momentum_elem / gd_elem.
@@ -765,6 +770,16 @@ int mv3d_adam_advance(void* state, void* stream) {
     return dispatch(stream, OpInfo{"adam_advance", 0.0, 16.0}, [=](hipStream_t s) {
         adam_advance_kernel<<<1, 64, 0, s>>>((float*)state);
         return launched("adam_advance_kernel");
+    });
+}
+
+int mv3d_opt_set_lr(void* state, float lr, void* stream) {
+    if (!state) return fail(MV3D_E_INVAL, "mv3d_opt_set_lr: null state");
+    if (((uintptr_t)state & 3)) return fail(MV3D_E_INVAL, "mv3d_opt_set_lr: the state must be 4-byte aligned");
+    if (!(lr >= 0.0f) || std::isinf(lr)) return fail(MV3D_E_INVAL, "mv3d_opt_set_lr: lr must be finite and >= 0");      // also refuses NaN
+    return dispatch(stream, OpInfo{"opt_set_lr", 0.0, 4.0}, [=](hipStream_t s) {
+        opt_set_lr_kernel<<<1, 64, 0, s>>>((float*)state, lr);
+        return launched("opt_set_lr_kernel");
     });
 }
 

@@ -1,31 +1,16 @@
 // Exponential moving average of the weights (tf.train.ExponentialMovingAverage, TF 1.3) and the in-place exchange that puts
 // the averaged weights where the forward pass reads them.  Built with -ffp-contract=off: the update is bit-exact against numpy.
-#include "common.h"
+#include "ema_common.h"
 #include <algorithm>
 #include <cmath>
 
 namespace mv3d {
 
-// moving_averages.assign_moving_average(shadow, var, decay, zero_debias=False) on one element, in TF's order:
-//   d = s - p;  u = d * w;  s = s - u      (w = 1 - decay, rounded once on the host).  s == p gives d = 0 and leaves s as it is.
-__device__ __forceinline__ float ema_elem(float s, float p, float w) {
-#pragma clang fp contract(off)
-    const float d = s - p;
-    const float u = d * w;
-    return s - u;
-}
-
-__device__ __forceinline__ float4 ema4(float4 s, float4 p, float w) {
-    return make_float4(ema_elem(s.x, p.x, w), ema_elem(s.y, p.y, w), ema_elem(s.z, p.z, w), ema_elem(s.w, p.w, w));
-}
-
+// (ema_elem, ema4 and the chunk geometry: ema_common.h, shared with weight_decay.hip)
 // A pure HBM stream, 12 B/param (loads s, p; stores s), no LDS.  A workgroup takes chunks of EMA_UNROLL x 256 float4s; every
 // lane issues its EMA_UNROLL 16-byte loads of BOTH buffers before the first use, so a workgroup has 2 x 4 x 4 KiB = 32 KiB of
 // loads in flight and a CU with several resident workgroups a multiple of that.  The grid is 8 workgroups per CU (256 CUs),
 // each walking the chunks with a grid stride; the last, partial chunk is bounds-checked, the count & 3 tail is scalar.
-constexpr int EMA_UNROLL = 4;
-constexpr int EMA_CHUNK = EMA_UNROLL * 256;      // float4s per workgroup per pass
-constexpr int EMA_MAX_BLOCKS = 2048;
 
 __global__ __launch_bounds__(256) void ema_kernel(int64_t count, float* __restrict__ s, const float* __restrict__ p, float w) {
     const int64_t nvec = count >> 2;

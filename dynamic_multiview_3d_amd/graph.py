@@ -56,6 +56,33 @@ def ema_rule(shadow, params, one_minus_decay):
     return s - u
 
 
+GLOBAL_STEP = 'global_step'                     # the checkpoint's count of optimiser updates (TF's global_step variable)
+
+
+def weight_decay_factor(lr, weight_decay):
+    """f = float32(float64(lr) * weight_decay), the scalar mv3d_weight_decay_step takes: rounded once."""
+    return np.float32(float(np.float32(lr)) * float(weight_decay))
+
+
+def weight_decay_rule(params, ranges, f, shadow=None, one_minus_decay=None):
+    """numpy twin of mv3d_weight_decay_step over whole flat float32 arrays: inside the [begin, end) index pairs of `ranges`
+    t = p * f; p = p - t with one rounding per operation, an element whose t is 0 keeping its bits (only p = -0 tells the
+    difference: its sign stays); outside them nothing.  Returns the new parameters, or with `shadow` (new parameters, new
+    shadows): the EMA of every element behind the decay, ema_rule(shadow, new parameters, one_minus_decay).  The inputs are
+    left alone; ranges that reach past the array are clipped."""
+    p = np.array(params, np.float32)
+    f = np.float32(f)
+    for a, b in np.asarray(ranges, np.int64).reshape(-1, 2):
+        a, b = max(int(a), 0), min(int(b), p.size)
+        if b > a:
+            with np.errstate(under='ignore'):
+                t = p[a:b] * f
+                p[a:b] = np.where(t == 0, p[a:b], p[a:b] - t)
+    if shadow is None:
+        return p
+    return p, ema_rule(shadow, p, one_minus_decay)
+
+
 # =============================================================================================== gradient-clipping host twin
 GN_CHUNK = 16384                                # floats per chunk of mv3d_grad_clip_scale (csrc/grad_norm.hip): 256 threads x 16 float4
 
@@ -728,6 +755,15 @@ class Graph:
         self.micro_step = 0             # position in the cycle, 0 .. N - 1
         self._accum_loss = None         # two floats: the running loss sum of the current cycle and the mean of the last completed one
         self._accum_slot, self._accum_done = 0, 1
+        # the count of optimiser updates made so far; update number k uses learning_rate_at(lr_spec, k).  A schedule
+        # (enable_lr_schedule) writes the next update's rate into the optimiser records behind each update; decoupled weight decay
+        # (enable_weight_decay) runs where the EMA launches run, over one device table of the decayed variables' flat ranges
+        self.global_step = 0
+        self.global_step_restored = False       # the last load_state_dict() found the counter in the checkpoint
+        self.lr_spec = None
+        self.weight_decay = None
+        self._decay_ranges = []         # [(begin, end)]: sorted, disjoint, multiples of 4
+        self._decay_table = None        # the same as int64 pairs on the device
 
     OPTIMIZERS = ('adam', 'momentum', 'sgd')
 
@@ -1215,9 +1251,112 @@ class Graph:
                 self._fc_ranges = [tuple(r) for r in skips]      # what the fused kernels and the bias launch update, on their stream
             else:
                 lib.plan_destroy(plan)
+        self._build_decay_table()
         self.upload_optimizer_state()
         self.reset_ema()
         return self
+
+    # ---------------------------------------------------------------- learning-rate schedule, weight decay
+    def enable_lr_schedule(self, spec):
+        """Update number k (0-based, Graph.global_step) uses lr_schedule.learning_rate_at(spec, k): call before compile() with
+        what lr_schedule_from_conf() returns; None leaves the switch off (the same plans, launches and bits).  Behind the last
+        launch of an update that reads an optimiser record, on that launch's stream, mv3d_opt_set_lr writes the NEXT update's
+        rate into it: a write in front of a step could race the previous update's fused fc launches still in flight."""
+        if spec is None:
+            return
+        if self.plan_fwd is not None:
+            raise RuntimeError("enable_lr_schedule: call it before compile()")
+        from .lr_schedule import learning_rate_at
+        learning_rate_at(spec, 0)           # a malformed spec raises here
+        self.lr_spec = dict(spec)
+
+    def enable_weight_decay(self, weight_decay):
+        """Decoupled weight decay: after update k, on the updated weights, p -= p * f_k with f_k = float32(float64(lr_k) *
+        weight_decay) -- the decay follows the scheduled rate, as torch.optim.AdamW scales it by the rate; it is applied BEHIND the
+        update rather than in front of it, which differs from AdamW's order by O(f * update).  Only variables with a gradient
+        whose name ends in /w or /Matrix decay; biases and variables without a gradient keep their bits.  Call before compile();
+        None or 0 leave the switch off (nothing allocated, the same plans and launches)."""
+        from .lr_schedule import check_weight_decay
+        wd = check_weight_decay(weight_decay, "enable_weight_decay: weight_decay")      # the conf key's own check
+        if wd is None:
+            return
+        if self.plan_fwd is not None:
+            raise RuntimeError("enable_weight_decay: call it before compile()")
+        self.weight_decay = wd
+
+    def counts_updates(self):
+        """True when a schedule, a warm-up or weight decay is on: checkpoints then carry `global_step`."""
+        return self.lr_spec is not None or self.weight_decay is not None
+
+    def learning_rate(self):
+        """The host float32 the next update will use (the device records hold the same bits)."""
+        if self.lr_spec is None:
+            return None if self.lr is None else np.float32(self.lr)
+        from .lr_schedule import learning_rate_at
+        return learning_rate_at(self.lr_spec, self.global_step)
+
+    def set_global_step(self, step):
+        """The count of updates made so far (a resume from a checkpoint that does not carry it: train.py hands in the iteration of
+        the file name); re-uploads the optimiser records with the rate of that update."""
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 0:
+            raise ValueError("set_global_step: step must be an integer >= 0, got %r" % (step,))
+        if self.accum_steps and self.micro_step:
+            raise RuntimeError("set_global_step() in the middle of an accumulation cycle (micro-step %d of %d)"
+                               % (self.micro_step, self.accum_steps))
+        self.global_step = int(step)
+        self.upload_optimizer_state()
+
+    def _build_decay_table(self):
+        """The decay set as ONE device table: the [begin, end) flat ranges of every variable with a gradient whose name ends in /w
+        or /Matrix, each padded to a multiple of 4 (the padding floats are zero and p - p * f keeps them zero)."""
+        self._decay_ranges, self._decay_table = [], None
+        if self.weight_decay is None:
+            return
+        pad4 = lambda v: (v.offset, v.offset + -(-v.size // 4) * 4)
+        self._decay_ranges = sorted(pad4(v) for k, v in self.variables.items()
+                                    if v.has_grad and k.rsplit('/', 1)[-1] in ('w', 'Matrix'))
+        n = len(self._decay_ranges)
+        if n > _lib.DECAY_MAX_RANGES:
+            raise ValueError("weight decay: %d decayed variables, mv3d_weight_decay_step takes at most %d ranges" % (n, _lib.DECAY_MAX_RANGES))
+        assert all(a % 4 == 0 and b % 4 == 0 and a < b for a, b in self._decay_ranges)
+        assert all(r[1] <= s[0] for r, s in zip(self._decay_ranges, self._decay_ranges[1:])) and (not n or self._decay_ranges[-1][1] <= self.flat_size)
+        self._decay_table = torch.tensor(self._decay_ranges or [(0, 0)], dtype=torch.int64).reshape(-1).to(self.device)
+
+    def _decay_factor(self):
+        """f_k of the update being issued (k = global_step): raises when it reaches 1."""
+        f = weight_decay_factor(self.learning_rate(), self.weight_decay)
+        if not f < 1.0:
+            raise ValueError("weight decay: f = float32(lr * weight_decay) = %r at update %d must stay below 1" % (float(f), self.global_step))
+        return float(f)
+
+    def _post_range(self, lo, hi, stream):
+        """What follows the optimiser over the flat range [lo, hi), on its stream: mv3d_weight_decay_step (with EMA on, its fused
+        form in place of the EMA launch, one for one), else mv3d_ema_step, else nothing."""
+        if self.weight_decay is not None:
+            ema = self.ema is not None
+            w = float(ema_one_minus_decay(self.ema_decay, self.ema_updates if self.ema_num_updates else None)) if ema else 0.0
+            self.lib.weight_decay_step(self.params.data_ptr(), self.ema.data_ptr() if ema else None, lo, hi,
+                                       self._decay_table.data_ptr(), len(self._decay_ranges), self._decay_factor(), w, stream)
+        elif self.ema is not None:
+            self._ema_range(lo, hi, stream)
+
+    def _lr_next(self, stream, main=True, fc=True):
+        """mv3d_opt_set_lr with the rate of update global_step + 1 into the main and / or the fused fc optimiser's record, behind
+        the last launch of update global_step that reads it, on that launch's stream.  Nothing without a schedule."""
+        if self.lr_spec is None:
+            return
+        from .lr_schedule import learning_rate_at
+        lr = float(learning_rate_at(self.lr_spec, self.global_step + 1))
+        if main:
+            self.lib.opt_set_lr(self.opt_state.data_ptr(), lr, stream)
+        if fc:
+            self.lib.opt_set_lr(self.opt_state.data_ptr() + 32, lr, stream)
+
+    def _update_done(self):
+        """Host bookkeeping of one optimiser update, once everything of it has been issued."""
+        if self.ema is not None:
+            self.ema_updates += 1
+        self.global_step += 1
 
     # ---------------------------------------------------------------- EMA weights
     def enable_ema(self, decay, num_updates=False):
@@ -1579,10 +1718,11 @@ class Graph:
         Nesterov flag; then the gradient scale (1 / world size; with gradient accumulation 1 / (world size * micro-steps))."""
         if self.opt_state is None or self.lr is None:
             return
+        lr = self.lr if self.lr_spec is None else self.learning_rate()      # a schedule: learning_rate_at(global_step)
         if self.optimizer == 'adam':
-            vals = [self.lr, self.beta1, self.beta2, self.eps, self.beta1_power, self.beta2_power]
+            vals = [lr, self.beta1, self.beta2, self.eps, self.beta1_power, self.beta2_power]
         else:
-            vals = [self.lr, self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0, 0.0, 0.0]
+            vals = [lr, self.momentum, 1.0 if self.use_nesterov else 0.0, 0.0, 0.0, 0.0]
         vals = np.array(vals + [1.0 / (self.world_size * max(self.accum_steps, 1)), 0.0], np.float32)
         self._settle()
         self.opt_state.copy_(torch.from_numpy(np.concatenate([vals, vals])))
@@ -1619,9 +1759,10 @@ class Graph:
         self._settle()
         self._opt_range(0, self.flat_size, self._stream_ptr())
         self._adam_advance()
-        if self.ema is not None:
-            self._ema_range(0, self.flat_size, self._stream_ptr())
-            self.ema_updates += 1
+        self._lr_next(self._stream_ptr())
+        if self.ema is not None or self.weight_decay is not None:
+            self._post_range(0, self.flat_size, self._stream_ptr())
+        self._update_done()
 
     apply_adam = apply_optimizer
 
@@ -1646,6 +1787,14 @@ class Graph:
         self._opt_range(lo, hi, fc_stream, self._bias_skip, state=fc_state)
         if self.optimizer == 'adam':
             self.lib.adam_advance(fc_state, fc_stream)
+        self._lr_next(fc_stream, main=False)     # the fc record: behind its last reader of this update, on the fc stream
+        decay = self.weight_decay is not None
+        if decay:
+            # the decay WRITES the fc matrices: it goes in front of _fc_event, which is what the next forward pass waits for before
+            # it reads them.  With EMA on it is the fused launch and the event is recorded behind it: the other placement, the
+            # pure decay in front of the event and the EMA behind it, measured 0.043 ms per step slower
+            for a, b in self._fc_ranges:
+                self._post_range(a, b, fc_stream)
         if pipelined:
             if self._fc_event is None:
                 self._fc_event = torch.cuda.Event()
@@ -1655,22 +1804,24 @@ class Graph:
         if not self._finalized_in_plan:          # otherwise the plan's last launch (grad_finalize_<kind>) was the optimiser of everything else
             self._opt_range(0, self.flat_size, st, (len(self._skip_lo), self._skip_lo, self._skip_hi))
         self._adam_advance(st, both=False)
-        if self.ema is not None:
+        self._lr_next(st, fc=False)
+        if self.ema is not None or decay:
             # every range behind its optimiser, on that optimiser's stream: the fused matrices and their layers' biases on the fc
-            # stream (behind _fc_event: the next forward pass does not wait for the EMA), the rest on the main stream (which has
-            # joined the stream of the grad_finalize launches).  The next step's writers of params fork from the main stream or
+            # stream (EMA alone behind _fc_event: the next forward pass does not wait for it), the rest on the main stream (which
+            # has joined the stream of the grad_finalize launches).  The next step's writers of params fork from the main stream or
             # sit on the fc stream, so they are behind these reads.
             at = 0
             for a, b in self._fc_ranges:
                 if a > at:
-                    self._ema_range(at, a, st)
-                self._ema_range(a, b, fc_stream)
+                    self._post_range(at, a, st)
+                if not decay:
+                    self._ema_range(a, b, fc_stream)
                 at = b
             if at < self.flat_size:
-                self._ema_range(at, self.flat_size, st)
-            if pipelined:
+                self._post_range(at, self.flat_size, st)
+            if pipelined and self.ema is not None and not decay:
                 self._ema_side(fcq)
-            self.ema_updates += 1
+        self._update_done()
 
     def run_backward_with_adam(self):
         """Single-GPU reverse pass with the optimiser folded in: the backward plan is issued bucket by bucket
@@ -1703,15 +1854,15 @@ class Graph:
                 if self.adam_timing is not None:
                     e1.record(self.adam_stream)
                     self.adam_timing.append((e0, e1))
-                if self.ema is not None:                # behind the slice's optimiser, on its stream (joined below)
-                    self._ema_range(plo, phi, self.adam_stream.cuda_stream)
+                if self.ema is not None or self.weight_decay is not None:       # behind the slice's optimiser, on its stream (joined below)
+                    self._post_range(plo, phi, self.adam_stream.cuda_stream)
             pending = []
         main.wait_stream(self.adam_stream)
         for st in (self.side_streams or []):
             main.wait_stream(st)
         self._adam_advance(main.cuda_stream)
-        if self.ema is not None:
-            self.ema_updates += 1
+        self._lr_next(main.cuda_stream)
+        self._update_done()
 
     run_backward_with_optimizer = run_backward_with_adam
 
@@ -1783,26 +1934,40 @@ class Graph:
                 comm.allgather_(self.params, lo, n, cs)
             if on_gpu:
                 ctx.__exit__(None, None, None)
-                if self._fc_event is None:
-                    self._fc_event = torch.cuda.Event()
-                self._fc_event.record(self.comm_stream)
-                self._fc_pending = True
-                self._pending_idx = late[0][0]
+        decay = with_adam and self.weight_decay is not None
+        if decay:
+            # ONE launch over the whole buffer on the communication stream, behind the last all-gather (late ones included) and IN
+            # FRONT of _fc_event: the decay writes the weights the next forward pass waits for.  Every rank decays identical
+            # parameters, so the weights stay bit-identical across ranks; with EMA on it is the fused form
+            self._post_range(0, self.flat_size, cs)
+        if late and on_gpu:
+            if self._fc_event is None:
+                self._fc_event = torch.cuda.Event()
+            self._fc_event.record(self.comm_stream)
+            self._fc_pending = True
+            # (with the decay the event covers weights of EVERY bucket, the conv filters the first forward launch reads among
+            # them: the next forward pass then waits in front of its first launch)
+            self._pending_idx = 0 if decay else late[0][0]
+        elif decay and on_gpu:
+            torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
         if with_adam:
             self._adam_advance()
-            if self.ema is not None:
+            self._lr_next(self._stream_ptr())
+            if self.ema is not None and not decay:
                 # ONE launch over the whole buffer on the communication stream, behind the last all-gather (late ones included)
                 # and behind _fc_event: every rank keeps the complete shadow of its (bit-identical) parameters
                 self._ema_range(0, self.flat_size, cs)
                 if on_gpu:
                     self._ema_side(self.comm_stream)
-                self.ema_updates += 1
+            self._update_done()
 
     def train_step(self):
         """forward + loss + reverse pass + (all-reduce) + optimiser (+ EMA of the weights); returns the device loss scalar.  With
         gradient accumulation one micro-step (run_micro_step): every accum_steps-th call updates, and the scalar returned is the
         micro-batch's loss (accum_loss() is the cycle's mean)."""
         self._check_not_swapped('train_step')
+        if self.weight_decay is not None:
+            self._decay_factor()            # f >= 1 raises before anything of the step is issued
         self.run_forward()
         if self.accum_steps:
             self.run_micro_step()
@@ -1870,7 +2035,9 @@ class Graph:
         """TF-Saver-style names: <var> and the active optimiser's slots -- <var>/Adam, <var>/Adam_1, beta1_power, beta2_power
         (Adam), <var>/Momentum (Momentum), nothing else (GD) -- (train.py:70-71 saves GLOBAL_VARIABLES).  With EMA on also
         <var>/ExponentialMovingAverage for EVERY variable (TF's shadow variables) and the update counter
-        ExponentialMovingAverage/num_updates; every data-parallel rank holds the complete shadows.  With gradient accumulation
+        ExponentialMovingAverage/num_updates; every data-parallel rank holds the complete shadows.  With a learning-rate schedule, a
+        warm-up or weight decay on also the int64 scalar global_step, the number of optimiser updates made (with all of them off
+        the keys are exactly those above).  With gradient accumulation
         it raises RuntimeError in the middle of a cycle: the partial gradient sum is not part of a checkpoint."""
         self._check_not_swapped('state_dict')
         if self.accum_steps and self.micro_step:
@@ -1894,17 +2061,25 @@ class Graph:
             sd['beta2_power'] = torch.tensor(float(self.beta2_power))
         if self.ema is not None:
             sd[EMA_COUNTER] = torch.tensor(float(self.ema_updates))
+        if self.counts_updates():           # only with a schedule, a warm-up or weight decay on: otherwise exactly the keys above
+            sd[GLOBAL_STEP] = torch.tensor(self.global_step, dtype=torch.int64)
         return sd
 
     def load_state_dict(self, sd):
         """Restores what state_dict() names; KeyError on a missing or unexpected entry.  With EMA on, a checkpoint that carries
         every shadow and the counter restores them; one that carries none is a resume that turns the switch on (shadows := the
         restored variables, counter := 0); one that carries some of them raises KeyError.  With EMA off shadow entries are
-        unexpected like any other."""
+        unexpected like any other.  With a schedule, a warm-up or weight decay on, global_step comes from the checkpoint, or is 0
+        where it has none (global_step_restored tells which; set_global_step() is the caller's remedy), and the optimiser records
+        are re-uploaded with the rate of that update."""
         self._check_not_swapped('load_state_dict')
         self._settle()
         slots = self._slots()
         names = {n for n, _ in slots}
+        step = None
+        if self.counts_updates():           # with the switches off `global_step` is unexpected like any other entry
+            sd = OrderedDict(sd)
+            step = sd.pop(GLOBAL_STEP, None)
         ema_keys = []
         if self.ema is not None:
             ema_keys = [k + '/' + EMA_SLOT for k in self.variables] + [EMA_COUNTER]
@@ -1946,6 +2121,9 @@ class Graph:
                 self.ema.copy_(self.params)
                 self.ema_updates = 0
         self.micro_step = 0             # an accumulation cycle starts afresh on the restored weights
+        if self.counts_updates():       # a checkpoint without the counter: 0 (train.py then hands in the file name's iteration)
+            self.global_step = 0 if step is None else int(step)
+            self.global_step_restored = step is not None
         self.upload_optimizer_state()
 
 

@@ -15,6 +15,8 @@ from . import tf_checkpoint
 from .graph import Graph, ema_one_minus_decay, ema_rule      # noqa: F401  (the numpy twins of mv3d_ema_step are part of this module's interface)
 from .graph import grad_clip_rule                            # noqa: F401  (... and the twin of mv3d_grad_clip_scale)
 from .graph import grad_accum_rule                           # noqa: F401  (... and the twin of mv3d_grad_accumulate)
+from .graph import weight_decay_rule, weight_decay_factor    # noqa: F401  (... and the twin of mv3d_weight_decay_step)
+from .lr_schedule import learning_rate_at, lr_schedule_from_conf, weight_decay_from_conf      # noqa: F401
 
 
 class Saver:
@@ -316,6 +318,8 @@ class ModelBase(object):
         grad_accum_from_conf(self.conf)  # ... and a bad conf['grad_accum_steps']
         from .augment import augment_from_conf
         augment_from_conf(self.conf)     # ... and a bad conf['augment_*'] (the input path's colour stage: augment.py)
+        lr_schedule_from_conf(self.conf)  # ... and a bad, stray or misspelt conf['lr_*']
+        weight_decay_from_conf(self.conf)  # ... and a bad conf['weight_decay']
         self.graph = Graph(device=device, seed=seed)
         return self.graph
 
@@ -333,6 +337,9 @@ class ModelBase(object):
         accum = grad_accum_from_conf(self.conf)
         if accum is not None and build_loss:    # likewise a property of the train step
             self.graph.enable_grad_accum(accum)
+        if build_loss:                          # the rate and the decay belong to the optimiser's update
+            self.graph.enable_lr_schedule(lr_schedule_from_conf(self.conf))
+            self.graph.enable_weight_decay(weight_decay_from_conf(self.conf))
         self.graph.compile()
 
     def ema_weights(self):

@@ -119,13 +119,17 @@ class SyntheticData:
         return b
 
 
-def training_log_row(model, itr, cost):
+def training_log_row(model, itr, cost, learning_rate=None):
     """The train_log.jsonl line of iteration itr: the loss, and with conf['grad_clip_norm'] / conf['grad_norm_log'] on the last
-    step's gradient norm (of the averaged gradient, before clipping) and clip scale.  Reading them synchronises, like float(cost)."""
+    step's gradient norm (of the averaged gradient, before clipping) and clip scale.  Reading them synchronises, like float(cost).
+    learning_rate: the rate that iteration's update used (the host mirror, read before the update: no synchronisation), given
+    whenever a schedule, a warm-up or weight decay is on."""
     row = {'itr': itr, 'training_loss': cost}
     if model.graph.clip_norm is not None:
         norm, scale = model.graph.grad_norm().tolist()
         row['grad_norm'], row['grad_clip_scale'] = norm, scale
+    if learning_rate is not None:
+        row['learning_rate'] = float(learning_rate)
     return row
 
 
@@ -148,15 +152,16 @@ def train_loop(model, conf, train_data, val_data, saver, itr_0=0, rank=0, log=No
     t_iter = []
     for itr in range(itr_0, conf['num_iterations'] + 1, 1):         # inclusive, train.py:117
         t_startiter = time.time()
+        lr = model.graph.learning_rate() if model.graph.counts_updates() else None      # the rate this iteration's update uses
         cost = train_iteration(model, train_data)
         if itr % 10 == 0:
             c = float(cost)
             if rank == 0:
                 print(str(itr) + ' ' + str(c))
-                row = training_log_row(model, itr, c)
+                row = training_log_row(model, itr, c, lr)
                 log.write(json.dumps(row) + '\n')
                 if events is not None:
-                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale'):
+                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale', 'learning_rate'):
                         if key in row:
                             log_value(events, row[key], key, itr)
         if itr % VAL_INTERVAL == 0 and itr != 0:
@@ -303,6 +308,9 @@ def main(argv=None):
         from .model_base import iteration_from_checkpoint_name
         itr_0 = iteration_from_checkpoint_name(conf['pretrained_model'])      # train.py:99-101
         print('resuming training at iteration:  ', itr_0)
+        g = model.graph
+        if g.counts_updates() and not g.global_step_restored:
+            g.set_global_step(itr_0)            # a checkpoint from before the switch: the schedule continues at the file name's iteration
 
     if rank == 0:
         print('-------------------------------------------------------------------')

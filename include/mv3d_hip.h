@@ -515,6 +515,38 @@ int mv3d_ema_step(int64_t count, void* shadow, const void* params, float one_min
  * Kernel label: swap_kernel. */
 int mv3d_swap_f32(int64_t count, void* a, void* b, void* stream);
 
+/* ---- scheduled learning rate: state[MV3D_ADAM_LR] (= state[MV3D_SGD_LR], float 0 of an 8-float optimiser record) = lr --------
+ * One workgroup, one plain store; the other 7 floats of the record are not touched.  The caller issues it with the rate of the
+ * NEXT update, behind the last launch of this update that reads the record and ON THAT LAUNCH'S STREAM: a write in front of a
+ * step could race the previous update's launches still in flight.  MV3D_E_INVAL: state NULL or not 4-byte aligned; lr negative,
+ * NaN or infinite.  Kernel label: opt_set_lr_kernel. */
+int mv3d_opt_set_lr(void* state, float lr, void* stream);
+
+/* ---- decoupled weight decay (the decay of torch.optim.AdamW, behind the optimiser's update), alone or with the EMA fused -------
+ * Over [lo, hi) intersected with a table of index ranges of the flat parameter buffer, per element, fp32, without contraction
+ * (bit-exact against numpy, graph.weight_decay_rule):
+ *   t = p * f;  p = p - t          f = float32(double(lr) * weight_decay), rounded once by the caller, in [0, 1)
+ * An element whose t is 0 (p = +-0, f = 0, an underflowing product) keeps its bits: that differs from the two operations only
+ * for p = -0, whose sign stays.
+ * params / shadow: the BASES of the flat buffers, 16-byte aligned; lo, hi, and the table's bounds are absolute element indices.
+ * ranges: DEVICE memory, nranges <= MV3D_DECAY_MAX_RANGES pairs of int64 [begin, end), sorted, disjoint, every bound a multiple
+ * of 4 (the caller guarantees it: the table is not read on the host); ranges may reach outside [lo, hi).  lo is a multiple of 4;
+ * hi is one too, or, in the fused form only, the unaligned end of the buffers (a scalar tail takes (hi - lo) & 3).  (The pure form
+ * refuses an unaligned hi: every range bound is a multiple of 4 and the entry cannot know where the buffer ends, so it cannot tell
+ * the buffer's end from a mistake; the feature's specification allowed the unaligned end in both forms -- a deliberate
+ * departure.  The graph's flat buffers are padded to multiples of 64 floats, so no caller of the project meets it.)
+ *   shadow == NULL  pure decay: a chunk (4096 floats) that meets no range is skipped without a load, elements outside the
+ *                   ranges are neither read nor written; 8 B of HBM traffic per decayed element.  one_minus_decay is ignored.
+ *   shadow != NULL  the EMA fused behind the decay: for EVERY element of [lo, hi)  d = s - p';  u = d * one_minus_decay;
+ *                   s = s - u  (mv3d_ema_step's three operations in its order), p' the decayed value inside the ranges and p
+ *                   outside them; 16 B per decayed element, 12 B elsewhere (the two separate launches move 8 + 12).
+ * MV3D_E_INVAL before any launch: params NULL; a misaligned buffer or table; lo < 0, hi <= lo, lo & 3, hi & 3 without a shadow;
+ * nranges outside 0 .. MV3D_DECAY_MAX_RANGES, or > 0 with ranges NULL; f outside [0, 1) or NaN; with a shadow one_minus_decay
+ * outside [0, 1] or NaN.  Kernel labels: weight_decay_kernel, weight_decay_kernel<fused>. */
+enum { MV3D_DECAY_MAX_RANGES = 1024 };
+int mv3d_weight_decay_step(void* params, void* shadow /* NULL: no EMA */, int64_t lo, int64_t hi, const void* ranges, int nranges,
+                           float f, float one_minus_decay, void* stream);
+
 /* ---- global-norm gradient clipping (the tf.clip_by_global_norm step of a TF-1.x trainer, over ONE flat gradient buffer) ------
  * n = ||g||_2 * pre_scale over `count` >= 1 floats; s = clip_norm / n where n > clip_norm, else 1; out[0] = n, out[1] = s, and
  * slot 6 (MV3D_ADAM_GSCALE / MV3D_SGD_GSCALE) of each optimiser record given becomes pre_scale * s: the optimiser launch that
