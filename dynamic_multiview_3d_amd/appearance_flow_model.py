@@ -15,6 +15,8 @@ class AppearanceFlowModel(ModelBase):
     supports_ssim_loss = True
     supports_flow_smoothness = True
     supports_multiscale_loss = True
+    supports_flow_consistency = True
+    supports_pair_swap = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
@@ -48,6 +50,7 @@ class AppearanceFlowModel(ModelBase):
         self.loss = self.loss + self.census_term(self.gen, self.image1)                                  # conf['census_loss_weight']
         self.loss = self.loss + self.flow_smoothness_term(self.flow_field, self.image1)                 # conf['flow_smoothness_weight']
         self.loss = self.loss + self.multiscale_term(self.flow_field, self.image0, self.image1)           # conf['multiscale_loss_levels']
+        self.loss = self.loss + self.flow_consistency_term(self.flow_field)                             # conf['flow_consistency_weight']
         self.train_op = optimizer_from_conf(self.conf, self.conf['learning_rate']).minimize(self.loss, self.graph)
 
     def eval_pairs(self):

@@ -298,8 +298,8 @@ class ScalarExpr:
     __rmul__ = __mul__
 
 
-LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CENSUS = 1, 2, 3, 4, 5, 6
-FLOW_TERMS = (LOSS_SMOOTH, LOSS_MULTISCALE)     # terms on a flow, usually an intermediate tensor: their gradient launch can be deferred
+LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CENSUS, LOSS_CONSIST = 1, 2, 3, 4, 5, 6, 7
+FLOW_TERMS = (LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST)     # terms on a flow, usually an intermediate tensor: their gradient launch can be deferred
 
 
 class LossTerm:
@@ -311,7 +311,9 @@ class LossTerm:
     consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  kind LOSS_MULTISCALE: the multi-scale
     photometric loss (mv3d_multiscale_warp_loss) of the flow a, merged the same way, that warps the third operand `src` onto the
     target b over `levels` pyramid levels with per-level weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2);
-    neither image is differentiated.  `ws` is an SSIM, census, smoothness or multi-scale term's own workspace, allocated by
+    neither image is differentiated.  kind LOSS_CONSIST: the forward-backward consistency (mv3d_flow_consistency) of the flow a
+    over a pair-swapped batch with Charbonnier eps, merged the same way; b is None.  `ws` is an SSIM, census, smoothness,
+    multi-scale or consistency term's own workspace, allocated by
     Graph.compile(); a multi-scale term's also holds the pyramids its forward call builds and its reverse call reuses."""
 
     def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3, src=None, levels=0,
@@ -962,7 +964,8 @@ class Graph:
         # value is recorded here and the gradient launch is deferred to the reverse plan (_smooth_before / _smooth_after).
         written = set()             # gradient addresses written by the terms so far
         # A multi-scale photometric term sits on the flow as well and is placed by the same rule, behind the smoothness terms.
-        order = lambda k: {LOSS_SSIM: 1, LOSS_CENSUS: 2, LOSS_SMOOTH: 3, LOSS_MULTISCALE: 4}.get(k, 0)
+        # A forward-backward consistency term does too, behind the multi-scale terms.
+        order = lambda k: {LOSS_SSIM: 1, LOSS_CENSUS: 2, LOSS_SMOOTH: 3, LOSS_MULTISCALE: 4, LOSS_CONSIST: 5}.get(k, 0)
         terms = sorted(self.loss_expr.terms, key=lambda wt: order(wt[1].kind))      # stable: the terms of a kind keep their order
         self._smooth_deferred = []
         for w, term in terms:
@@ -996,7 +999,8 @@ class Graph:
                 _note_grad_written(a, False)
 
     def _smooth_launch(self, w, term, value, grad, accumulate):
-        """One call of a term on a flow (mv3d_flow_smoothness for LOSS_SMOOTH, mv3d_multiscale_warp_loss for LOSS_MULTISCALE): the
+        """One call of a term on a flow (mv3d_flow_smoothness for LOSS_SMOOTH, mv3d_multiscale_warp_loss for LOSS_MULTISCALE,
+        mv3d_flow_consistency for LOSS_CONSIST): the
         value into the loss word and / or the gradient stored into or added onto the flow's gradient buffer.  A multi-scale call
         without the value is the reverse-pass call: the value call of this step has left the pyramids in the term's workspace."""
         a, b = term.a, term.b
@@ -1010,6 +1014,13 @@ class Graph:
                                           term.pixel_kind, self.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None,
                                           a.ld, 1 if (grad and accumulate) else 0, 0 if value else 1, term.ws.data_ptr(), term.ws.numel(),
                                           self.stream)
+            if grad:
+                _note_grad_written(a, False)
+            return
+        if term.kind == LOSS_CONSIST:
+            self.lib.flow_consistency(n, h, wd, a.ptr, a.ld, term.eps, float(w), self.loss_buf.data_ptr() if value else None, None,
+                                      a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, term.ws.data_ptr(),
+                                      term.ws.numel(), self.stream)
             if grad:
                 _note_grad_written(a, False)
             return
@@ -1075,6 +1086,11 @@ class Graph:
                 nbytes = int(lib.flow_smoothness_workspace_bytes(*term.a.shape[:3]))
                 if not nbytes:
                     raise ValueError("flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (term.a.shape,))
+                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            if term.kind == LOSS_CONSIST and term.ws is None:    # the int64 scatter plane, the float plane of the gathered part and the tile sums
+                nbytes = int(lib.flow_consistency_workspace_bytes(*term.a.shape[:3]))
+                if not nbytes:
+                    raise ValueError("flow_consistency_loss: a flow of shape %s is outside what mv3d_flow_consistency takes" % (term.a.shape,))
                 term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             if term.kind == LOSS_MULTISCALE and term.ws is None:     # the tile sums and the pyramids of src and target
                 s = term.src

@@ -367,6 +367,142 @@ def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, gra
     return out
 
 
+# ------------------------------------------------------------------------------------------------ forward-backward flow consistency
+def _consist_scalars(eps, weight):
+    """(eps, weight) as the floats the C ABI takes; ValueError on what mv3d_flow_consistency would refuse."""
+    eps, weight = (float(np.float32(v)) for v in (eps, weight))
+    if not math.isfinite(eps) or eps <= 0:
+        raise ValueError("flow_consistency: eps must be finite and positive")
+    if not float(np.float32(eps) * np.float32(eps)) >= float(np.finfo(np.float32).tiny):
+        raise ValueError("flow_consistency: eps (%g) is below 2^-63: eps * eps underflows in float32, and with it the exact zeros" % eps)
+    if not math.isfinite(weight):
+        raise ValueError("flow_consistency: weight must be finite")
+    return eps, weight
+
+
+def _consist_shape(shape):
+    if len(shape) != 4 or shape[3] != 2:
+        raise ValueError("flow_consistency: flow must be [N,H,W,2], got %s" % (tuple(shape),))
+    if shape[0] < 2 or shape[0] % 2:
+        raise ValueError("flow_consistency: flow %s needs an even N >= 2 (the second half holds the reversed pairs)" % (tuple(shape),))
+    if shape[1] != shape[2] or shape[1] < 2:
+        raise ValueError("flow_consistency: flow %s needs H == W >= 2 (the transposed sampler convention)" % (tuple(shape),))
+
+
+def flow_consistency_host(flow, eps=1e-3, dtype=np.float64, weight=1.0):
+    """(loss, grad, value, valid_fraction) of the forward-backward consistency of a pair-swapped batch of flows [N,H,W,2] (N even,
+    H == W): loss = weight * C and value = C are scalars of `dtype`, grad = d loss / d flow is [N,H,W,2] in `dtype`; every step in
+    `dtype` arithmetic.  At float32 this states mv3d_flow_consistency's own operation order (csrc/flow_consist.hip); only the sum
+    behind C (the kernel keeps it in double) and the scatter (the kernel sums it in 64-bit fixed point) differ.
+
+      partner of sample n: m = (n + N/2) mod N
+      x = f[..., 0] + i (the ROW index),  y = f[..., 1] + j: the sampler reads x as the column and y as the row (the transposed
+          convention of warp_pts_layer + resample_layer)
+      valid = 0 <= x <= W-1 and 0 <= y <= H-1 (NaN, inf: not valid); stricter than the sampler's window, so no tap with a non-zero
+          weight is outside the image.  A tap at index W or H has weight 0, reads 0 and receives nothing
+      w = (dx dy, (1-dx)(1-dy), dx (1-dy), (1-dx) dy) for the taps ff cc fc cf of flow[m];  s = ((w0 ff + w1 cc) + w2 fc) + w3 cf
+      r0 = f0 + s1,  r1 = f1 + s0 (the channel swap belongs to the convention),  d = sqrt((r0 r0 + r1 r1) + eps eps)
+      phi = d - eps,  psi = (r0 / d, r1 / d);   C = sum over valid of phi / (N H W);  valid_fraction = count(valid) / (N H W)
+      k = weight / (N H W);  gx = psi1 (dy (cf0 - ff0) + (1-dy) (cc0 - fc0)) + psi0 (the same of channel 1), gy with dx and
+          (fc - ff), (cc - cf): the sampler's warp gradient for dgen = (psi1, psi0)
+      grad[n,i,j] = ((psi0 + gx) k, (psi1 + gy) k) where valid;   grad[m, tap q] += (w_q psi1, w_q psi0) summed, then times k
+    Flows that invert each other on integer offsets, (a, b) against (-b, -a), give exactly (0, zeros, 0, .)."""
+    dtype = np.dtype(dtype).type
+    f = np.asarray(flow).astype(dtype)
+    _consist_shape(f.shape)
+    eps, weight = _consist_scalars(eps, weight)
+    n, h, w, _ = f.shape
+    half = n // 2
+    npix = float(n) * h * w
+    one, zero = dtype(1), dtype(0)
+    eps_t = dtype(eps)
+    eps2 = eps_t * eps_t
+    partner = np.roll(f, -half, axis=0)                      # partner[n] = f[(n + N/2) mod N]
+    ii, jj = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing='ij')
+    x = f[..., 0] + ii[None]
+    y = f[..., 1] + jj[None]
+    with np.errstate(invalid='ignore'):
+        valid = (x >= 0) & (y >= 0) & (x <= w - 1) & (y <= h - 1)
+    xs, ys = np.where(valid, x, zero), np.where(valid, y, zero)
+    fxf, fyf = np.floor(xs), np.floor(ys)
+    dx, dy = (fxf + one) - xs, (fyf + one) - ys
+    fx, fy = fxf.astype(np.int64), fyf.astype(np.int64)
+    b = np.broadcast_to(np.arange(n).reshape(n, 1, 1), x.shape)
+
+    taps = []                                                # (ok, row, column, values) of ff, cc, fc, cf
+    for yy, xx in ((fy, fx), (fy + 1, fx + 1), (fy + 1, fx), (fy, fx + 1)):
+        ok = valid & (xx < w) & (yy < h)
+        yc, xc = np.minimum(yy, h - 1), np.minimum(xx, w - 1)
+        taps.append((ok, yc, xc, np.where(ok[..., None], partner[b, yc, xc], zero)))
+    wq = (dx * dy, (one - dx) * (one - dy), dx * (one - dy), (one - dx) * dy)
+    iff, icc, ifc, icf = (t[3] for t in taps)
+    s = ((wq[0][..., None] * iff + wq[1][..., None] * icc) + wq[2][..., None] * ifc) + wq[3][..., None] * icf
+    r0, r1 = f[..., 0] + s[..., 1], f[..., 1] + s[..., 0]
+    d = np.sqrt((r0 * r0 + r1 * r1) + eps2)
+    phi = np.where(valid, d - eps_t, zero)
+    psi0, psi1 = np.where(valid, r0 / d, zero), np.where(valid, r1 / d, zero)
+    c = float(phi.sum(dtype=dtype)) / npix
+    value, loss = dtype(c), dtype(weight * c)
+    valid_fraction = dtype(float(np.count_nonzero(valid)) / npix)
+    k = dtype(weight / npix)
+
+    gx = np.zeros(x.shape, dtype)
+    gy = np.zeros(x.shape, dtype)
+    for ch, g in ((0, psi1), (1, psi0)):                     # channels added in index order
+        gx = gx + g * (dy * (icf[..., ch] - iff[..., ch]) + (one - dy) * (icc[..., ch] - ifc[..., ch]))
+        gy = gy + g * (dx * (ifc[..., ch] - iff[..., ch]) + (one - dx) * (icc[..., ch] - icf[..., ch]))
+    grad = np.where(valid[..., None], np.stack(((psi0 + gx) * k, (psi1 + gy) * k), axis=-1), zero).astype(dtype)
+    scat = np.zeros(f.shape, dtype)
+    mb = (b + half) % n
+    def finite(v):                                           # a non-finite entry (a non-finite partner flow) is dropped, as by the kernel
+        return np.where(np.isfinite(v), v, zero)
+    for q, (ok, yc, xc, _) in enumerate(taps):
+        np.add.at(scat, (mb[ok], yc[ok], xc[ok], 0), finite(wq[q] * psi1)[ok])
+        np.add.at(scat, (mb[ok], yc[ok], xc[ok], 1), finite(wq[q] * psi0)[ok])
+    grad = grad + scat * k
+    return loss, grad, value, valid_fraction
+
+
+def flow_consistency(flow, eps=1e-3, weight=1.0, grad=None, accumulate=False, stats=None, stream=None):
+    """mv3d_flow_consistency on device memory: weight * C of flow_consistency_host, and optionally its gradient with respect to the
+    flow.  flow: a graph Tensor (channel views included) or a torch device tensor, float32 [N,H,W,2], N even, H == W.  grad: an
+    optional float32 device tensor of the flow's shape with one pixel stride (a channel slice of a dense tensor works); it is
+    overwritten, or added to when accumulate is true.  stats: an optional dense float32 [2] device tensor that receives the
+    unweighted C and the valid fraction.  Asynchronous on `stream` (default: torch's current stream of the operands' device).
+    Returns the loss as a 0-d device tensor."""
+    import torch
+    from . import _lib
+    pf, shape, f_ld, dev = _operand(flow, 'flow')
+    _consist_shape(shape)
+    eps, weight = _consist_scalars(eps, weight)              # the twin's checks: the same ValueError for the same argument
+    dev = torch.device(dev)
+    if dev.type != 'cuda':
+        raise _lib.Mv3dError("flow_consistency runs on the GPU (operands are on %s); flow_consistency_host is the numpy form" % dev)
+    n, h, w, _ = shape
+    pg, g_ld = None, 2
+    if grad is not None:
+        if not torch.is_tensor(grad):
+            raise ValueError("flow_consistency: grad must be a torch device tensor")
+        pg, shape_gr, g_ld, dev_gr = _operand(grad, 'grad')
+        if shape_gr != shape or not _same_device(dev_gr, dev):
+            raise ValueError("flow_consistency: grad %s on %s does not match flow %s on %s" % (shape_gr, dev_gr, shape, dev))
+    ps = None
+    if stats is not None:
+        if (not torch.is_tensor(stats) or tuple(stats.shape) != (2,) or stats.dtype != torch.float32 or not stats.is_contiguous()
+                or not _same_device(stats.device, dev)):
+            raise ValueError("flow_consistency: stats must be a dense float32 [2] tensor on the flow's device")
+        ps = stats.data_ptr()
+    out = torch.zeros((), dtype=torch.float32, device=dev)
+    lib = _lib.lib()
+    nbytes = int(lib.flow_consistency_workspace_bytes(n, h, w))
+    ws = _workspace(dev, nbytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.flow_consistency(n, h, w, pf, f_ld, float(eps), float(weight), out.data_ptr(), ps, pg, g_ld, 1 if accumulate else 0,
+                         ws.data_ptr(), nbytes, stream)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ multi-scale photometric loss
 MULTISCALE_MAX_LEVELS = 3
 

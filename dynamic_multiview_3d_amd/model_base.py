@@ -204,6 +204,33 @@ def flow_smoothness_from_conf(conf):
     return w, alpha, eps
 
 
+def flow_consistency_from_conf(conf):
+    """(weight, eps) of the forward-backward consistency switch: conf['flow_consistency_weight'] (0.0 when absent, None or 0, which
+    leaves the loss and the recorded plans as they are) and conf['flow_consistency_eps'] (the Charbonnier epsilon in pixels,
+    default 1e-3).  A positive weight needs conf['pair_swap'] (pair_swap.py): without it the two halves of a batch are unrelated
+    samples and the term means nothing.  Raises ValueError on a bool, a negative or non-finite weight, a bad eps, or a positive
+    weight without conf['pair_swap'], before any device work."""
+    from .pair_swap import pair_swap_from_conf
+    w = conf.get('flow_consistency_weight')
+    if isinstance(w, bool):
+        raise ValueError("conf['flow_consistency_weight'] must be a number >= 0 (or None for off), got %r" % (w,))
+    w = 0.0 if w is None else float(w)
+    if not np.isfinite(w) or w < 0:
+        raise ValueError("conf['flow_consistency_weight'] must be finite and >= 0, got %r" % (conf['flow_consistency_weight'],))
+    eps = conf.get('flow_consistency_eps')
+    if isinstance(eps, bool):
+        raise ValueError("conf['flow_consistency_eps'] must be a number > 0, got %r" % (eps,))
+    eps = 1e-3 if eps is None else float(eps)
+    if not np.isfinite(eps) or eps <= 0:
+        raise ValueError("conf['flow_consistency_eps'] must be finite and > 0, got %r" % (conf['flow_consistency_eps'],))
+    if not float(np.float32(eps) * np.float32(eps)) >= float(np.finfo(np.float32).tiny):
+        raise ValueError("conf['flow_consistency_eps'] must be at least 2^-63 (its square must not underflow in float32), got %r" % (eps,))
+    if w > 0 and not pair_swap_from_conf(conf):
+        raise ValueError("conf['flow_consistency_weight'] needs conf['pair_swap'] = True: the term pairs sample n of a batch with "
+                         "sample n + batch_size / 2, which the pair-swapped feed makes the reversed pair")
+    return w, eps
+
+
 def multiscale_loss_from_conf(conf):
     """(levels, [w_1 .. w_levels], kind) of the multi-scale photometric switch: conf['multiscale_loss_levels'] (1..3; absent, None
     or 0 = off), conf['multiscale_loss_weight'] (a scalar applied to every level or a list of one weight per level, default 1.0)
@@ -239,6 +266,8 @@ class ModelBase(object):
     supports_ssim_loss = False      # the classes whose build_loss() adds ssim_term() and census_term() set it
     supports_flow_smoothness = False        # the classes whose build_loss() adds flow_smoothness_term() set it
     supports_multiscale_loss = False        # the classes whose build_loss() adds multiscale_term() set it
+    supports_flow_consistency = False       # the classes whose build_loss() adds flow_consistency_term() set it
+    supports_pair_swap = False              # the classes whose inputs are exactly the reader's five tensors (pair_swap.py)
 
     def _check_conf(self):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
@@ -250,6 +279,25 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['flow_smoothness_weight']" % type(self).__name__)
         if multiscale_loss_from_conf(self.conf)[0] > 0 and not self.supports_multiscale_loss:
             raise ValueError("%s has no flow: it does not support conf['multiscale_loss_levels']" % type(self).__name__)
+        from .pair_swap import pair_swap_from_conf
+        if pair_swap_from_conf(self.conf) and not self.supports_pair_swap:
+            raise ValueError("%s does not support conf['pair_swap']: its inputs are not the five reader tensors of one pair, so "
+                             "a sample has no reverse" % type(self).__name__)
+        if flow_consistency_from_conf(self.conf)[0] > 0 and not self.supports_flow_consistency:
+            raise ValueError("%s does not support conf['flow_consistency_weight']" % type(self).__name__)
+
+    def flow_consistency_term(self, flow, name='flow'):
+        """conf['flow_consistency_weight'] * flow_consistency_loss(flow, eps) on one flow head, or 0 when the switch is absent or 0
+        (the graph then records exactly what it recorded without the key).  evaluate() reports the unweighted term as
+        '<name>/consistency' and the share of valid pixels as '<name>/consistency_valid'."""
+        from .tf_utils import flow_consistency_loss
+        w, eps = flow_consistency_from_conf(self.conf)
+        if w == 0:
+            return 0
+        if not hasattr(self, 'consistency_terms'):
+            self.consistency_terms = []         # [(name, flow, eps)]
+        self.consistency_terms.append((name, flow, eps))
+        return flow_consistency_loss(flow, eps) * w
 
     def multiscale_term(self, flow, src, target, name='flow'):
         """multiscale_photometric_loss(flow, src, target) with the levels, weights and kind of conf['multiscale_loss_*'] on one flow
@@ -411,6 +459,9 @@ class ModelBase(object):
         With conf['multiscale_loss_levels'] on, every flow head's unweighted level terms T_l (the level_values of
         mv3d_multiscale_warp_loss; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/photo_x2',
         '<head>/photo_x4' and '<head>/photo_x8'.
+        With conf['flow_consistency_weight'] > 0 the unweighted forward-backward consistency C of the flow head and its share of
+        valid pixels (the stats of mv3d_flow_consistency; numpy form on a CPU graph), averaged over the batches, are reported as
+        '<head>/consistency' and '<head>/consistency_valid'.
         With conf['census_loss_weight'] > 0 the unweighted census term of every pair that carries one (mv3d_census_loss; numpy
         form on a CPU graph), averaged over the batches, is reported as '<pair>/census'.
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
@@ -429,18 +480,21 @@ class ModelBase(object):
         ms_terms = getattr(self, 'multiscale_terms', [])
         ms_kind = {'l1': 1, 'l2': 2}
         census_terms = getattr(self, 'census_terms', [])
+        consist_terms = getattr(self, 'consistency_terms', [])
         if on_gpu:
             scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
             losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
             smooth = torch.zeros((num_batches, len(smooth_terms)), dtype=torch.float32, device=g.device)
             photo = torch.zeros((num_batches, len(ms_terms), 3), dtype=torch.float32, device=g.device)
             census = torch.zeros((num_batches, len(census_terms)), dtype=torch.float32, device=g.device)
+            consist = torch.zeros((num_batches, len(consist_terms), 2), dtype=torch.float32, device=g.device)
         else:
             scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
             losses = np.zeros(num_batches, np.float64)
             smooth = np.zeros((num_batches, len(smooth_terms)), np.float64)
             photo = np.zeros((num_batches, len(ms_terms), 3), np.float64)
             census = np.zeros((num_batches, len(census_terms)), np.float64)
+            consist = np.zeros((num_batches, len(consist_terms), 2), np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
             if on_gpu:
@@ -452,6 +506,8 @@ class ModelBase(object):
                     photo[i, j, :levels].copy_(metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1], non_blocking=True)
                 for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
                     census[i, j].copy_(metrics.census_loss(pred, target, max_val, 1.0, radius, eps), non_blocking=True)
+                for j, (_, flow, eps) in enumerate(consist_terms):
+                    metrics.flow_consistency(flow, eps, 1.0, stats=consist[i, j])
                 if have_loss:
                     losses[i].copy_(loss, non_blocking=True)
             else:
@@ -465,16 +521,20 @@ class ModelBase(object):
                                                                              ms_kind[kind])[2]
                 for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
                     census[i, j] = float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0])
+                for j, (_, flow, eps) in enumerate(consist_terms):
+                    consist[i, j] = [float(v) for v in metrics.flow_consistency_host(flow.numpy(), eps)[2:]]
                 if have_loss:
                     losses[i] = float(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1)]).cpu()          # the one synchronisation
+            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1), consist.reshape(-1)]).cpu()          # the one synchronisation
             scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
             losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
             at = scores.size + num_batches
             smooth = packed[at:at + smooth.numel()].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
             photo = packed[at + smooth.size:at + smooth.size + photo.numel()].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
-            census = packed[at + smooth.size + photo.size:].numpy().astype(np.float64).reshape(num_batches, len(census_terms))
+            at += smooth.size + photo.size
+            census = packed[at:at + census.numel()].numpy().astype(np.float64).reshape(num_batches, len(census_terms))
+            consist = packed[at + census.size:].numpy().astype(np.float64).reshape(num_batches, len(consist_terms), 2)
         result = {}
         if have_loss:
             result['loss'] = float(losses.mean())
@@ -490,6 +550,9 @@ class ModelBase(object):
                 result['%s/photo_x%d' % (term[0], 2 << l)] = float(photo[:, j, l].mean())
         for j, term in enumerate(census_terms):
             result[term[0] + '/census'] = float(census[:, j].mean())
+        for j, term in enumerate(consist_terms):
+            result[term[0] + '/consistency'] = float(consist[:, j, 0].mean())
+            result[term[0] + '/consistency_valid'] = float(consist[:, j, 1].mean())
         result['images'] = num_batches * n
         return result
 

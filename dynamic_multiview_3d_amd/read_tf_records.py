@@ -333,7 +333,10 @@ class TFRecordInput:
     With conf['augment_*'] (augment.py) a training input (training=True and no test_mode) runs the colour stage on every batch: on
     the device mv3d_color_augment in the input thread, on the reader's stream, behind the conversion kernels and before the batch's
     event is recorded; with device='cpu' the numpy twin.  Validation, --evaluate and --visualize inputs never build it, and with
-    the keys absent nothing is built and the batches are the plain reader's."""
+    the keys absent nothing is built and the batches are the plain reader's.
+    With conf['pair_swap'] (pair_swap.py) a batch is made of batch_size / 2 records and their reverses: the files and records
+    come in the order they have without the key, consumed half as fast, and the mirror stage runs on the reader's stream behind
+    the colour stage (which then draws one map per record), for training, validation, --evaluate and --visualize inputs alike."""
 
     def __init__(self, conf, input_shapes, training=True, device='cpu', seed=0, prefetch=4, verify=True, rank=0, world=1):
         self.files = split_files(conf, training)
@@ -350,11 +353,15 @@ class TFRecordInput:
         self.rng = np.random.default_rng(seed)
         self.device, self.verify = device, verify
         self.q = queue.Queue(maxsize=max(prefetch, 1))
+        from .pair_swap import pair_swap_from_conf, PairSwap
+        self.pair_swap = PairSwap(conf, self.batch) if pair_swap_from_conf(conf) else None
+        self.nrec = self.pair_swap.half if self.pair_swap is not None else self.batch        # records per batch
         self.augment = None
         if training and 'test_mode' not in conf:
             from . import augment
             if augment.augment_from_conf(conf).enabled:      # a generator of its own: the shuffle order does not depend on the switch
-                self.augment = augment.ColorAugment(conf, input_shapes, device=device, rank=rank, ring=self.q.maxsize + 2)
+                shapes = {k: (self.nrec,) + tuple(s[1:]) for k, s in input_shapes.items()} if self.pair_swap is not None else input_shapes
+                self.augment = augment.ColorAugment(conf, shapes, device=device, rank=rank, ring=self.q.maxsize + 2)
         self._stop = False
         self._err = None
         self.thread = threading.Thread(target=self._produce, daemon=True)
@@ -389,7 +396,7 @@ class TFRecordInput:
             nring = self.q.maxsize + 2                    # a staging set is reused only after its upload has completed
             ring = []
             for _ in range(nring):
-                bufs = [torch.empty((self.batch,) + self.rspec[k], dtype=torch.float32 if kd else torch.uint8) for k, kd in zip(names, kinds)]
+                bufs = [torch.empty((self.nrec,) + self.rspec[k], dtype=torch.float32 if kd else torch.uint8) for k, kd in zip(names, kinds)]
                 if cuda:
                     bufs = [b.pin_memory() for b in bufs]
                 ring.append((bufs, (C.c_void_p * len(names))(*[b.data_ptr() for b in bufs]), [None]))
@@ -403,14 +410,14 @@ class TFRecordInput:
                 if done[0] is not None:
                     done[0].synchronize()
                 have = 0
-                while have < self.batch:
+                while have < self.nrec:
                     if reader is None:
                         reader = C.c_void_p()
                         lib.tfrecord_open(next(files).encode(), 1 if self.verify else 0, C.byref(reader))
-                    lib.tfrecord_read(reader, self.batch - have, have, len(names), c_names, c_kinds, c_sizes, c_dst, C.byref(nread))
+                    lib.tfrecord_read(reader, self.nrec - have, have, len(names), c_names, c_kinds, c_sizes, c_dst, C.byref(nread))
                     have += nread.value
                     dry = 0 if nread.value > 0 else dry + 1
-                    if have < self.batch:                 # end of this file
+                    if have < self.nrec:                  # end of this file
                         lib.tfrecord_close(reader)
                         reader = None
                         if dry > len(self.files):
@@ -421,7 +428,7 @@ class TFRecordInput:
                         for k, kd, rs, b in zip(names, kinds, resize, bufs):
                             d = b.to(self.device, non_blocking=True)
                             if rs:
-                                f = torch.empty((self.batch,) + self.spec[k], dtype=torch.float32, device=self.device)
+                                f = torch.empty((self.nrec,) + self.spec[k], dtype=torch.float32, device=self.device)
                                 lib.u8_process_image(d.data_ptr(), *d.shape, f.data_ptr(), *self.spec[k][:2], stream.cuda_stream)
                                 d = f
                             elif not kd:
@@ -431,6 +438,8 @@ class TFRecordInput:
                             out[k] = d
                         if self.augment is not None:
                             self.augment.apply(out, stream)
+                        if self.pair_swap is not None:
+                            out = self.pair_swap.apply(out, stream)
                         ev = torch.cuda.Event()
                         ev.record(stream)
                     done[0] = ev
@@ -443,6 +452,8 @@ class TFRecordInput:
                             out[k] = b.clone() if kd else b.to(torch.float32) / np.float32(255.0)
                     if self.augment is not None:
                         self.augment.apply(out)
+                    if self.pair_swap is not None:
+                        out = self.pair_swap.apply(out)
                 self.q.put((out, ev))
         except BaseException as e:       # surfaced by next()
             self._err = e

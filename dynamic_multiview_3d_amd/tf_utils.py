@@ -7,7 +7,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_CENSUS, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_CENSUS, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
                     CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
@@ -197,6 +197,26 @@ def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=N
         raise NotImplementedError("multiscale_photometric_loss: the images are not differentiated; they must not require a gradient")
     return ScalarExpr([(1.0, LossTerm(flow, target, LOSS_MULTISCALE, src=src_img, levels=levels, level_weights=weights,
                                       pixel_kind=LOSS_L2 if kind == 'l2' else LOSS_L1))])
+
+
+def flow_consistency_loss(flow, eps=1e-3):
+    """Forward-backward consistency of a flow field [N,H,W,2] over a pair-swapped batch (mv3d_flow_consistency;
+    metrics.flow_consistency_host states the definition): sample n + N/2 is sample n read backwards (pair_swap.py), and following
+    the flow of n and then the partner's flow there should lead back to the start; the mean Charbonnier penalty
+    sqrt(|r|^2 + eps^2) - eps of that residual over the pixels that stay inside the image.  N must be even and the field square.
+    The flow must be differentiated (it is usually an intermediate tensor: its gradient from the consumer and this term's are
+    added).  Masked and scaled operands are not supported."""
+    from .metrics import _consist_scalars, _consist_shape
+    if isinstance(flow, (_Masked, _Scaled)):
+        raise NotImplementedError("flow_consistency_loss of a masked or scaled operand")
+    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
+        raise ValueError("flow_consistency_loss: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
+    _check_usable(flow)
+    _consist_shape(flow.shape)
+    if not flow.requires_grad:
+        raise ValueError("flow_consistency_loss: the flow is not differentiated (nothing to regularise)")
+    eps, _ = _consist_scalars(float(eps), 1.0)
+    return ScalarExpr([(1.0, LossTerm(flow, None, LOSS_CONSIST, eps=eps))])
 
 
 # ------------------------------------------------------------------------------------------------ activations

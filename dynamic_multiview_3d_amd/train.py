@@ -30,6 +30,8 @@ With conf['augment_brightness' / '_saturation' / '_hue' / '_contrast'] (augment.
 one colour map per sample over all of its colour views: the TFRecord reader runs it on its own stream, and synthetic training batches
 are handed out as augmented copies (the cycled pool stays pristine).  Validation, --evaluate and --visualize batches are never augmented;
 under data parallelism every rank draws from np.random.default_rng([augment_seed, rank]).
+With conf['pair_swap'] (pair_swap.py) every batch is conf['batch_size'] / 2 pairs and their reverses, for every input of the graph;
+conf['flow_consistency_weight'] adds the forward-backward consistency term that layout makes possible.
 """
 import argparse
 import importlib
@@ -281,6 +283,12 @@ def main(argv=None):
             # the pool is cycled: without this the same four batches would repeat forever.  Copies, so that the pool stays pristine
             shapes = {k: tuple(t.shape) for k, t in model.graph.inputs.items()}
             train_data = augment.AugmentedData(train_data, augment.ColorAugment(conf, shapes, device=model.graph.device, rank=rank))
+        from . import pair_swap
+        if pair_swap.pair_swap_from_conf(conf):
+            # the first half of every synthetic batch and its reverses, behind the colour stage: the layout the graph's batch has
+            # for training, validation, --evaluate and --visualize alike
+            stage = pair_swap.PairSwap(conf, next(iter(model.graph.inputs.values())).shape[0])       # the graph's batch, as the reader takes it
+            train_data, val_data = pair_swap.PairSwappedData(train_data, stage), pair_swap.PairSwappedData(val_data, stage)
 
     if FLAGS.visualize:                                               # train.py:80-92
         print('-------------------------------------------------------------------')

@@ -288,7 +288,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss, mv3d_flow_consistency) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -459,6 +459,57 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
                               const void* target, int target_ld, int levels, const float* level_weights, int kind, void* loss_accum,
                               void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* ---- forward-backward flow consistency over pair-swapped batches: value and gradient with respect to the flow --------------
+ * flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view works), N even, H == W >= 2.  The second half of the batch
+ * holds the reversed pairs of the first (pair_swap.py): the partner of sample n is m = (n + N/2) mod N.  The sampler's convention
+ * is the transposed one of mv3d_warp_resample_fwd: channel 0 + the ROW index is x (column), channel 1 + the COLUMN index is y
+ * (row); it is why the images must be square and why the residual swaps the channels of the sample.  For pixel (i, j) of sample
+ * n, f = flow[n,i,j,:]:
+ *   x = f0 + i,  y = f1 + j;   valid iff 0 <= x <= W-1 and 0 <= y <= H-1 (NaN and inf are not): stricter than the sampler's
+ *   -1 < x < W window, so that no tap with a non-zero weight lies outside the image (a flow does not fade to black)
+ *   s = the bilinear sample of flow[m] at (row y, column x), both channels, with the sampler's tap and weight expressions; a tap
+ *   at index W or H occurs only with weight 0, reads 0 and receives no gradient
+ *   r0 = f0 + s1,  r1 = f1 + s0,  d = sqrt(r0^2 + r1^2 + eps^2),  phi = d - eps,  psi = (r0 / d, r1 / d)
+ *   C = (sum over the valid pixels of phi) / (N H W),   valid_fraction = (valid pixels) / (N H W): the normaliser is fixed, an
+ *   invalid pixel contributes 0 to the value and to every gradient
+ *   loss_accum[0] += weight * C, or = weight * C when mv3d_loss_overwrite_next() is pending on the calling thread (the flag is
+ *   consumed; a recorded call keeps what it saw; a call with loss_accum NULL leaves it pending).  One thread adds, in stream order.
+ *   stats (optional, device, 2 floats; needs loss_accum) receives the unweighted C and valid_fraction.
+ *   With k = weight / (N H W), grad (pixel stride grad_ld >= 2) receives
+ *     gathered  at [n,i,j]: ((psi0 + gx) k, (psi1 + gy) k), with (gx, gy) what mv3d_warp_resample_bwd gives for data = flow[m]
+ *               and dgen = (psi1, psi0); 0 for an invalid pixel
+ *     scattered at every tap q of flow[m] with weight w_q: (w_q psi1, w_q psi0) summed over the pixels, the sum times k
+ *   as grad = gathered + scattered (one fp32 addition): stored when grad_accumulate == 0, added onto what is there with one more
+ *   fp32 addition when grad_accumulate == 1 (accumulate == contents + the stored gradient, bit for bit); one writer per element.
+ *   The scatter is summed in 64-bit fixed point: llrint(w_q psi 2^K) is added with integer atomics into an int64 plane
+ *   [N,H,W,2] in the workspace (cleared inside the call), K = 62 - ceil(log2(H W)) (48 at 128 x 128, never below 32).  An
+ *   element receives at most one tap from each of the H W pixels of the partner sample and |w_q psi| < 1, so a sum stays within
+ *   H W 2^K <= 2^62: overflow would need more than H W entries at one element, which cannot happen.  The tiled pass leaves the
+ *   gathered part in a float2 plane of the workspace; a last pass converts the integer sum to fp32, multiplies by k, adds the
+ *   gathered part and writes grad.  Error of the scattered
+ *   part at an element: at most (entries at that element) * 2^-(K+1) * |k|, plus the one fp32 rounding of the conversion.
+ * A non-finite value of flow[m] at a tap of a valid pixel makes that pixel's phi and psi NaN, as in the numpy twin: C and the
+ * pixel's own gathered gradient are then NaN (the error stays visible), while its scattered entries, which the integer plane
+ * cannot hold, are dropped (the twin drops them too).
+ * loss_accum and grad are each optional, not both NULL.  Channels outside the views are never written.
+ * Every step is fp32 without contraction in the order of metrics.py flow_consistency_host at float32 (sqrt and division
+ * correctly rounded); only the sum behind C (double, fixed order), the valid count (integer-valued, exact) and the fixed-point
+ * scatter differ from it.  Flows that invert each other on integer offsets, flow[n] = (a, b) and flow[m] = (-b, -a), give a value
+ * of exactly 0 and gathered and scattered gradients of exactly 0 wherever the pixel is valid.  No floating-point atomics; the same
+ * inputs give the same bits run after run, under plan replay, and for grad_accumulate 0 against 1 onto zeros; the value's bits
+ * do not depend on whether a gradient was asked for.  No state outside `workspace` (16-byte aligned,
+ * mv3d_flow_consistency_workspace_bytes() bytes, 0 for a shape the entry refuses): the int64 plane, the gathered plane and the per-tile sums.
+ * Launches (plan labels): flow_consist_tile, flow_consist_scatter (only with grad), flow_consist_final.
+ * MV3D_E_INVAL before any launch: N < 2 or odd; H != W; H < 2 or H > 32768; N * ceil(H/16) * ceil(W/64) >= 2^31 or an element
+ * index that overflows; flow_ld < 2; grad_ld < 2; grad_accumulate outside {0, 1}; eps not finite, <= 0, or below 2^-63 (about
+ * 1.1e-19: eps * eps must be a normal fp32 number, or its root is not eps again and the exact zeros are lost); weight not finite;
+ * flow NULL; loss_accum and grad both NULL; stats without loss_accum; workspace NULL; flow, loss_accum, stats or grad not 4-byte
+ * aligned.  MV3D_E_WORKSPACE: workspace too small or not 16-byte aligned.  On any error loss_accum, stats and grad are left
+ * untouched and a pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_flow_consistency_workspace_bytes(int N, int H, int W);
+int mv3d_flow_consistency(int N, int H, int W, const void* flow, int flow_ld, float eps, float weight, void* loss_accum, void* stats,
+                          void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
