@@ -75,6 +75,9 @@ STATUS_FUNCS = {
     "mv3d_census_loss": [_i, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_smoothness": [_i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_consistency": [_i, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp],
+    "mv3d_flow_occlusion_mask": [_i, _i, _i, _vp, _i, _f, _f, _i, _vp, _i, _vp, _vp, _sz, _vp],
+    "mv3d_warp_resample_occlusion_loss": [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _i, _vp, _i,
+                                          _vp, _vp, _vp, _sz, _vp],
     "mv3d_multiscale_warp_loss": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _i, _i, _i,
                                   _vp, _sz, _vp],
     "mv3d_pixel_loss": [_i64, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
@@ -145,6 +148,8 @@ OTHER_FUNCS = {
     "mv3d_census_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_flow_consistency_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mv3d_flow_occlusion_mask_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mv3d_warp_resample_occlusion_loss_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_multiscale_warp_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "mv3d_grad_clip_workspace_bytes": (_sz, [_i64]),
     "mv3d_color_augment_workspace_bytes": (_sz, [_i, _i, _i, _i]),

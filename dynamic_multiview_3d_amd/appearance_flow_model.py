@@ -17,6 +17,7 @@ class AppearanceFlowModel(ModelBase):
     supports_multiscale_loss = True
     supports_flow_consistency = True
     supports_pair_swap = True
+    supports_occlusion_mask = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf
@@ -46,7 +47,8 @@ class AppearanceFlowModel(ModelBase):
         return lrelu(linear_msra(a1, 64, "a2"))
 
     def build_loss(self):
-        self.loss = euclidean_loss(self.gen, self.image1) + self.ssim_term(self.gen, self.image1)      # conf['ssim_loss_weight']
+        # head_loss(): euclidean_loss(gen, image1), or its occlusion-masked form with conf['occlusion_mask']
+        self.loss = self.head_loss(self.gen, self.image1, self.flow_field) + self.ssim_term(self.gen, self.image1)      # conf['ssim_loss_weight']
         self.loss = self.loss + self.census_term(self.gen, self.image1)                                  # conf['census_loss_weight']
         self.loss = self.loss + self.flow_smoothness_term(self.flow_field, self.image1)                 # conf['flow_smoothness_weight']
         self.loss = self.loss + self.multiscale_term(self.flow_field, self.image0, self.image1)           # conf['multiscale_loss_levels']

@@ -34,6 +34,7 @@ UNITS = {
     "flow_smooth.hip": ["-ffp-contract=off"],
     "multiscale_loss.hip": ["-ffp-contract=off"],
     "flow_consist.hip": ["-ffp-contract=off"],
+    "flow_occlusion.hip": ["-ffp-contract=off"],
     "comm.hip": [],                     # RCCL resolved at run time (dlsym): no link-time dependency
     "tfrecord.hip": ["-msse4.2"],       # host code only: the input thread's record reader (hardware crc32c)
 }

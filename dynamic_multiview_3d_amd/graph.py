@@ -603,6 +603,8 @@ class ResampleNode(Node):
     def __init__(self, src, flow, warp, gen):
         self.src, self.flow, self.warp, self.gen = src, flow, warp, gen
         self.fused_loss = None      # (weight, LossTerm) when gen feeds exactly one plain pixel loss (Graph._fuse_resample_losses)
+        self.fused_occlusion = None     # the OcclusionMaskNode whose mask that loss carries: the occlusion-aware head in one launch
+        self.occlusion_ws = None        # ... and its workspace (the per-tile sums)
 
     def workspace_bytes(self, g):
         if not self.src.requires_grad:
@@ -618,6 +620,17 @@ class ResampleNode(Node):
             # sampler + loss + sampler gradient in one pass: the loss gradient d(gen) never goes to HBM
             wgt, term = self.fused_loss
             want_grad = self.flow.requires_grad
+            if self.fused_occlusion is not None:
+                # ... and the occlusion mask of that loss is made on the way (mv3d_warp_resample_occlusion_loss)
+                o = self.fused_occlusion
+                g.lib.warp_resample_occlusion_loss(n, h, w, hs, ws, c, self.src.ptr, self.flow.ptr, self.flow.ld, term.b.ptr, term.b.ld,
+                                                   term.kind, float(wgt), o.alpha1, o.alpha2, 1 if o.outside_visible else 0,
+                                                   self.warp.ptr, self.gen.ptr, self.flow.grad_ptr if want_grad else None, self.flow.ld,
+                                                   o.mask.ptr, o.mask.ld, g.loss_buf.data_ptr(), None, self.occlusion_ws.data_ptr(),
+                                                   self.occlusion_ws.numel(), g.stream)
+                if want_grad:
+                    _note_grad_written(self.flow, False)
+                return
             g.lib.warp_resample_loss(n, h, w, hs, ws, c, self.src.ptr, self.flow.ptr, self.flow.ld, term.b.ptr, term.b.ld,
                                      term.kind, float(wgt), self.warp.ptr, self.gen.ptr,
                                      self.flow.grad_ptr if want_grad else None, self.flow.ld, g.loss_buf.data_ptr(), g.stream)
@@ -640,6 +653,25 @@ class ResampleNode(Node):
             g.lib.resampler_bwd(n, h * w, hs, ws, c, self.src.ptr, self.src.ld, self.warp.ptr, 2, self.gen.grad_ptr, self.gen.ld,
                                 None, 0, self.src.grad_ptr, self.src.ld, g.ws_ptr, g.ws_bytes, g.stream)
             _note_grad_written(self.src, False)
+
+
+class OcclusionMaskNode(Node):
+    """tf_utils.occlusion_mask: flow [N,H,W,2] of a pair-swapped batch -> the one-channel occlusion mask [N,H,W,1]
+    (mv3d_flow_occlusion_mask; metrics.flow_occlusion_mask_host states the definition).  The mask is a constant of the step: it has
+    no gradient.  `fused_into` is the ResampleNode whose fused launch (mv3d_warp_resample_occlusion_loss) writes the mask instead
+    of this node's own launch (Graph._fuse_resample_losses)."""
+
+    def __init__(self, flow, mask, alpha1, alpha2, outside_visible):
+        self.flow, self.mask = flow, mask
+        self.alpha1, self.alpha2, self.outside_visible = float(alpha1), float(alpha2), bool(outside_visible)
+        self.fused_into = None
+
+    def forward(self, g):
+        if self.fused_into is not None:
+            return
+        n, h, w, _ = self.flow.shape
+        g.lib.flow_occlusion_mask(n, h, w, self.flow.ptr, self.flow.ld, self.alpha1, self.alpha2, 1 if self.outside_visible else 0,
+                                  self.mask.ptr, self.mask.ld, None, None, 0, g.stream)
 
 
 class ResamplerNode(Node):
@@ -880,13 +912,19 @@ class Graph:
     def _fuse_resample_losses(self):
         """A resampler output that is consumed by exactly one unmasked, unscaled pixel loss and by no other node (the
         appearance-flow head, appearance_flow_model.py:127-130 + build_loss) is computed together with that loss and
-        the flow gradient by mv3d_warp_resample_loss.  MV3D_FUSE_RESAMPLE=0 keeps the three separate launches."""
+        the flow gradient by mv3d_warp_resample_loss.  A loss whose mask is the occlusion mask of the resampler's own flow
+        (OcclusionMaskNode) fuses too, into mv3d_warp_resample_occlusion_loss, which writes the mask in place of the node's own
+        launch.  MV3D_FUSE_RESAMPLE=0 keeps the separate launches."""
         self.fused_terms = set()
         enabled = os.environ.get('MV3D_FUSE_RESAMPLE', '1') != '0'
+        for n in self.nodes:
+            if isinstance(n, OcclusionMaskNode):
+                n.fused_into = None
         for n in self.nodes:
             if not isinstance(n, ResampleNode):
                 continue
             n.fused_loss = None
+            n.fused_occlusion = None
             if not enabled or self.loss_expr is None or n.src.requires_grad:
                 continue            # the sampled image's gradient has to exist when the source needs one
             gen = n.gen
@@ -897,8 +935,20 @@ class Graph:
             w, t = uses[0]
             if t.kind in (LOSS_SSIM, LOSS_CENSUS):
                 continue            # the SSIM and census losses need gen and write their gradient in HBM: they never fuse
-            if t.a is not gen or t.mask is not None or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
+            if t.a is not gen or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
                 continue
+            occl = None
+            if t.mask is not None:
+                # A masked loss fuses only when the mask is the occlusion mask of the resampler's own flow: the fused launch then
+                # makes it (mv3d_warp_resample_occlusion_loss).  The mask node has to come behind the resampler, so that nothing in
+                # front of the fused launch can have read the mask.
+                occl = t.mask.producer
+                if not (isinstance(occl, OcclusionMaskNode) and occl.mask is t.mask and occl.flow is n.flow and occl.fused_into is None
+                        and self.nodes.index(occl) > self.nodes.index(n)):
+                    continue
+                bn, bh, bw, _ = n.flow.shape
+                if tuple(n.src.shape[:3]) != (bn, bh, bw) or bh != bw or bn % 2 or bn < 2:
+                    continue
             if gen.C > 4 or gen.ld != gen.C or gen.storage.has_alias or gen.storage.alias_of is not None:
                 continue
             read_elsewhere = False
@@ -911,6 +961,14 @@ class Graph:
                         read_elsewhere = True
             if read_elsewhere:
                 continue
+            if occl is not None:
+                nbytes = int(self.lib.warp_resample_occlusion_loss_workspace_bytes(*n.flow.shape[:3]))
+                if not nbytes:
+                    continue
+                if n.occlusion_ws is None or n.occlusion_ws.numel() != nbytes:
+                    n.occlusion_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                n.fused_occlusion = occl
+                occl.fused_into = n
             n.fused_loss = (w, t)
             self.fused_terms.add(id(t))
 

@@ -503,6 +503,112 @@ def flow_consistency(flow, eps=1e-3, weight=1.0, grad=None, accumulate=False, st
     return out
 
 
+# ------------------------------------------------------------------------------------------------ occlusion mask of the head loss
+def _occlusion_scalars(alpha1, alpha2, outside_visible):
+    """(alpha1, alpha2, outside_visible) as the values the C ABI takes; ValueError on what mv3d_flow_occlusion_mask would refuse."""
+    if isinstance(alpha1, bool) or isinstance(alpha2, bool):
+        raise ValueError("flow_occlusion_mask: alpha1 and alpha2 must be numbers")
+    alpha1, alpha2 = (float(np.float32(v)) for v in (alpha1, alpha2))
+    if not math.isfinite(alpha1) or alpha1 < 0:
+        raise ValueError("flow_occlusion_mask: alpha1 must be finite and >= 0")
+    if not math.isfinite(alpha2) or alpha2 <= 0:
+        raise ValueError("flow_occlusion_mask: alpha2 must be finite and positive")
+    if not isinstance(outside_visible, (bool, np.bool_)):
+        raise ValueError("flow_occlusion_mask: outside_visible must be True or False, got %r" % (outside_visible,))
+    return alpha1, alpha2, bool(outside_visible)
+
+
+def flow_occlusion_mask_host(flow, alpha1=0.01, alpha2=0.5, outside_visible=True, dtype=np.float64, details=False):
+    """(mask [N,H,W] of `dtype`, (visible, occluded, outside) shares of N H W as floats) of a pair-swapped batch of flows [N,H,W,2]
+    (N even, H == W): the forward-backward occlusion test of UnFlow in the conventions of flow_consistency_host, every step in
+    `dtype` arithmetic.  At float32 this states mv3d_flow_occlusion_mask's own operation order (csrc/flow_occlusion.hip).
+
+      partner of sample n: m = (n + N/2) mod N;   x = f[..., 0] + i (the ROW index),  y = f[..., 1] + j
+      inside = 0 <= x <= W-1 and 0 <= y <= H-1 (NaN, inf: not inside): the consistency term's strict window
+      w = (dx dy, (1-dx)(1-dy), dx (1-dy), (1-dx) dy) for the taps ff cc fc cf of flow[m];  s = ((w0 ff + w1 cc) + w2 fc) + w3 cf
+      r0 = f0 + s1,  r1 = f1 + s0;   lhs = r0 r0 + r1 r1;   rhs = alpha1 ((f0 f0 + f1 f1) + (s0 s0 + s1 s1)) + alpha2
+      visible = inside and lhs < rhs (a NaN on either side: not visible, the pixel counts as occluded)
+      mask = 1 where visible, 0 where inside and not visible, and (1 if outside_visible else 0) where not inside
+    The mask has no gradient.  With details=True a third result (lhs, rhs, inside) is returned, for tests that need the margins."""
+    dtype = np.dtype(dtype).type
+    f = np.asarray(flow).astype(dtype)
+    _consist_shape(f.shape)
+    alpha1, alpha2, outside_visible = _occlusion_scalars(alpha1, alpha2, outside_visible)
+    n, h, w, _ = f.shape
+    half = n // 2
+    one, zero = dtype(1), dtype(0)
+    a1, a2 = dtype(np.float32(alpha1)), dtype(np.float32(alpha2))
+    partner = np.roll(f, -half, axis=0)                      # partner[n] = f[(n + N/2) mod N]
+    ii, jj = np.meshgrid(np.arange(h, dtype=dtype), np.arange(w, dtype=dtype), indexing='ij')
+    x = f[..., 0] + ii[None]
+    y = f[..., 1] + jj[None]
+    with np.errstate(invalid='ignore'):
+        inside = (x >= 0) & (y >= 0) & (x <= w - 1) & (y <= h - 1)
+    xs, ys = np.where(inside, x, zero), np.where(inside, y, zero)
+    fxf, fyf = np.floor(xs), np.floor(ys)
+    dx, dy = (fxf + one) - xs, (fyf + one) - ys
+    fx, fy = fxf.astype(np.int64), fyf.astype(np.int64)
+    b = np.broadcast_to(np.arange(n).reshape(n, 1, 1), x.shape)
+    taps = []                                                # values of ff, cc, fc, cf
+    for yy, xx in ((fy, fx), (fy + 1, fx + 1), (fy + 1, fx), (fy, fx + 1)):
+        ok = inside & (xx < w) & (yy < h)
+        yc, xc = np.minimum(yy, h - 1), np.minimum(xx, w - 1)
+        taps.append(np.where(ok[..., None], partner[b, yc, xc], zero))
+    wq = (dx * dy, (one - dx) * (one - dy), dx * (one - dy), (one - dx) * dy)
+    with np.errstate(invalid='ignore', over='ignore'):
+        s = ((wq[0][..., None] * taps[0] + wq[1][..., None] * taps[1]) + wq[2][..., None] * taps[2]) + wq[3][..., None] * taps[3]
+        f0, f1 = f[..., 0], f[..., 1]
+        r0, r1 = f0 + s[..., 1], f1 + s[..., 0]
+        lhs = r0 * r0 + r1 * r1
+        rhs = a1 * ((f0 * f0 + f1 * f1) + (s[..., 0] * s[..., 0] + s[..., 1] * s[..., 1])) + a2
+        visible = inside & (lhs < rhs)
+    mask = np.where(inside, np.where(visible, one, zero), one if outside_visible else zero).astype(dtype)
+    npix = float(n) * h * w
+    shares = (np.count_nonzero(visible) / npix, np.count_nonzero(inside & ~visible) / npix, np.count_nonzero(~inside) / npix)
+    if details:
+        return mask, shares, (lhs, rhs, inside)
+    return mask, shares
+
+
+def flow_occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True, out=None, stats=None, stream=None):
+    """mv3d_flow_occlusion_mask on device memory: the mask of flow_occlusion_mask_host.  flow: a graph Tensor (channel views
+    included) or a torch device tensor, float32 [N,H,W,2], N even, H == W.  out: an optional float32 device tensor [N,H,W] or
+    [N,H,W,1] with one pixel stride (a channel of a wider tensor works); a dense [N,H,W,1] tensor is made when it is None.  stats:
+    an optional dense float32 [3] device tensor that receives the visible, occluded and outside shares.  Asynchronous on `stream`
+    (default: torch's current stream of the operands' device).  Returns the mask tensor."""
+    import torch
+    from . import _lib
+    pf, shape, f_ld, dev = _operand(flow, 'flow')
+    _consist_shape(shape)
+    alpha1, alpha2, outside_visible = _occlusion_scalars(alpha1, alpha2, outside_visible)
+    dev = torch.device(dev)
+    if dev.type != 'cuda':
+        raise _lib.Mv3dError("flow_occlusion_mask runs on the GPU (operands are on %s); flow_occlusion_mask_host is the numpy form" % dev)
+    n, h, w, _ = shape
+    if out is None:
+        out = torch.empty((n, h, w, 1), dtype=torch.float32, device=dev)
+    if not torch.is_tensor(out):
+        raise ValueError("flow_occlusion_mask: out must be a torch device tensor")
+    view = out if out.dim() == 4 else out.unsqueeze(-1)
+    po, shape_o, o_ld, dev_o = _operand(view, 'out')
+    if shape_o != (n, h, w, 1) or not _same_device(dev_o, dev):
+        raise ValueError("flow_occlusion_mask: out %s on %s does not match flow %s on %s" % (tuple(out.shape), dev_o, shape, dev))
+    ps = None
+    if stats is not None:
+        if (not torch.is_tensor(stats) or tuple(stats.shape) != (3,) or stats.dtype != torch.float32 or not stats.is_contiguous()
+                or not _same_device(stats.device, dev)):
+            raise ValueError("flow_occlusion_mask: stats must be a dense float32 [3] tensor on the flow's device")
+        ps = stats.data_ptr()
+    lib = _lib.lib()
+    nbytes = int(lib.flow_occlusion_mask_workspace_bytes(n, h, w)) if ps is not None else 0
+    ws = _workspace(dev, nbytes) if nbytes else None
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    lib.flow_occlusion_mask(n, h, w, pf, f_ld, float(alpha1), float(alpha2), 1 if outside_visible else 0, po, o_ld, ps,
+                            ws.data_ptr() if ws is not None else None, nbytes, stream)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ multi-scale photometric loss
 MULTISCALE_MAX_LEVELS = 3
 

@@ -231,6 +231,50 @@ def flow_consistency_from_conf(conf):
     return w, eps
 
 
+def occlusion_from_conf(conf):
+    """None, or (alpha1, alpha2, outside_visible) of the occlusion-mask switch: conf['occlusion_mask'] (absent, None or False = off,
+    which leaves the loss and the recorded plans as they are), conf['occlusion_alpha1'] (default 0.01), conf['occlusion_alpha2']
+    (default 0.5, in pixels squared) and conf['occlusion_outside'] ('keep', the default: a pixel whose flow leaves the image keeps
+    its loss, or 'mask': it loses it, UnFlow's choice).  The switch needs conf['pair_swap'] (pair_swap.py): the mask comes from the
+    forward-backward residual of sample n against sample n + batch_size / 2.  The SSIM, census and multi-scale terms have no
+    masked form: combined with conf['ssim_loss_weight'], conf['census_loss_weight'] or conf['multiscale_loss_levels'] the switch
+    is refused.  Raises ValueError on a non-bool switch, a bool, negative or non-finite alpha1, an alpha2 <= 0, an unknown
+    conf['occlusion_outside'], a missing conf['pair_swap'] or one of those combinations, before any device work."""
+    from .pair_swap import pair_swap_from_conf
+    on = conf.get('occlusion_mask')
+    if on is not None and not isinstance(on, (bool, np.bool_)):
+        raise ValueError("conf['occlusion_mask'] must be True or False (or None for off), got %r" % (on,))
+    alphas = []
+    for key, default in (('occlusion_alpha1', 0.01), ('occlusion_alpha2', 0.5)):
+        v = conf.get(key)
+        if isinstance(v, (bool, np.bool_)) or isinstance(v, str):
+            raise ValueError("conf[%r] must be a number, got %r" % (key, v))
+        v = default if v is None else float(v)
+        if not np.isfinite(v) or not np.isfinite(np.float32(v)):
+            raise ValueError("conf[%r] must be finite, got %r" % (key, conf[key]))
+        alphas.append(v)
+    if alphas[0] < 0:
+        raise ValueError("conf['occlusion_alpha1'] must be >= 0, got %r" % (conf['occlusion_alpha1'],))
+    if alphas[1] <= 0 or not float(np.float32(alphas[1])) > 0:
+        raise ValueError("conf['occlusion_alpha2'] must be > 0, got %r" % (conf['occlusion_alpha2'],))
+    outside = conf.get('occlusion_outside')
+    outside = 'keep' if outside is None else outside
+    if outside not in ('keep', 'mask'):
+        raise ValueError("conf['occlusion_outside'] must be 'keep' or 'mask', got %r" % (outside,))
+    if not on:
+        return None
+    if not pair_swap_from_conf(conf):
+        raise ValueError("conf['occlusion_mask'] needs conf['pair_swap'] = True: the mask pairs sample n of a batch with sample "
+                         "n + batch_size / 2, which the pair-swapped feed makes the reversed pair")
+    if ssim_weight_from_conf(conf) > 0:
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['ssim_loss_weight']: the SSIM loss has no masked form")
+    if census_from_conf(conf)[0] > 0:
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['census_loss_weight']: the census loss has no masked form")
+    if multiscale_loss_from_conf(conf)[0] > 0:
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['multiscale_loss_levels']: the multi-scale loss has no masked form")
+    return alphas[0], alphas[1], outside == 'keep'
+
+
 def multiscale_loss_from_conf(conf):
     """(levels, [w_1 .. w_levels], kind) of the multi-scale photometric switch: conf['multiscale_loss_levels'] (1..3; absent, None
     or 0 = off), conf['multiscale_loss_weight'] (a scalar applied to every level or a list of one weight per level, default 1.0)
@@ -268,6 +312,7 @@ class ModelBase(object):
     supports_multiscale_loss = False        # the classes whose build_loss() adds multiscale_term() set it
     supports_flow_consistency = False       # the classes whose build_loss() adds flow_consistency_term() set it
     supports_pair_swap = False              # the classes whose inputs are exactly the reader's five tensors (pair_swap.py)
+    supports_occlusion_mask = False         # the classes whose build_loss() takes its photometric term from head_loss()
 
     def _check_conf(self):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
@@ -285,6 +330,45 @@ class ModelBase(object):
                              "a sample has no reverse" % type(self).__name__)
         if flow_consistency_from_conf(self.conf)[0] > 0 and not self.supports_flow_consistency:
             raise ValueError("%s does not support conf['flow_consistency_weight']" % type(self).__name__)
+        if occlusion_from_conf(self.conf) is not None and not self.supports_occlusion_mask:
+            raise ValueError("%s does not support conf['occlusion_mask']" % type(self).__name__)
+
+    def head_loss(self, gen, target, flow, name='flow'):
+        """The photometric term of an appearance-flow head: euclidean_loss(gen, target), exactly the reference's, when
+        conf['occlusion_mask'] is absent, None or False (the graph then records what it recorded without the key); with the key on,
+        masked_euclidean_loss(gen, target, occlusion_mask(flow, alpha1, alpha2, outside)) with the mask held constant.  The
+        consistency term (conf['flow_consistency_weight']) stays unmasked: it is what keeps 'every pixel occluded' from being a
+        minimum of the masked loss.  evaluate() reports the mask's shares as '<name>/visible', '<name>/occluded', '<name>/outside'."""
+        from .tf_utils import euclidean_loss, masked_euclidean_loss, occlusion_mask
+        occl = occlusion_from_conf(self.conf)
+        if occl is None:
+            return euclidean_loss(gen, target)
+        mask = occlusion_mask(flow, *occl)
+        if not hasattr(self, 'occlusion_terms'):
+            self.occlusion_terms = []           # [(name, flow, mask tensor, alpha1, alpha2, outside_visible)]
+        self.occlusion_terms.append((name, flow, mask) + tuple(occl))
+        return masked_euclidean_loss(gen, target, mask)
+
+    def occlusion_mask(self, name='flow'):
+        """The occlusion mask [B,H,W,1] of the last step (forward, train or evaluate) as a device tensor: a view of the graph's
+        own buffer, overwritten by the next step.  Needs conf['occlusion_mask']."""
+        for term in getattr(self, 'occlusion_terms', []):
+            if term[0] == name:
+                return term[2].value()
+        raise RuntimeError("occlusion_mask: the model was built without conf['occlusion_mask'] (or without a loss)")
+
+    def flow_visible(self, name='flow'):
+        """The visible share of the last step's mask as a 0-d device tensor (train.py logs it: a mask that collapses shows here).
+        One extra launch pair on the current flow; not part of the step."""
+        from . import metrics
+        for term in getattr(self, 'occlusion_terms', []):
+            if term[0] == name:
+                if self.graph.device.type != 'cuda':        # a CPU graph: the numpy form
+                    return metrics.flow_occlusion_mask_host(term[1].numpy(), term[3], term[4], term[5])[1][0]
+                stats = torch.zeros(3, dtype=torch.float32, device=self.graph.device)
+                metrics.flow_occlusion_mask(term[1], term[3], term[4], term[5], stats=stats)
+                return stats[0]
+        raise RuntimeError("flow_visible: the model was built without conf['occlusion_mask'] (or without a loss)")
 
     def flow_consistency_term(self, flow, name='flow'):
         """conf['flow_consistency_weight'] * flow_consistency_loss(flow, eps) on one flow head, or 0 when the switch is absent or 0
@@ -464,6 +548,9 @@ class ModelBase(object):
         '<head>/consistency' and '<head>/consistency_valid'.
         With conf['census_loss_weight'] > 0 the unweighted census term of every pair that carries one (mv3d_census_loss; numpy
         form on a CPU graph), averaged over the batches, is reported as '<pair>/census'.
+        With conf['occlusion_mask'] on, the visible, occluded and outside shares of the head's occlusion mask (the stats of
+        mv3d_flow_occlusion_mask; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/visible',
+        '<head>/occluded' and '<head>/outside'.
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
         from . import metrics
         g = self.graph
@@ -481,6 +568,7 @@ class ModelBase(object):
         ms_kind = {'l1': 1, 'l2': 2}
         census_terms = getattr(self, 'census_terms', [])
         consist_terms = getattr(self, 'consistency_terms', [])
+        occl_terms = getattr(self, 'occlusion_terms', [])
         if on_gpu:
             scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
             losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
@@ -488,6 +576,7 @@ class ModelBase(object):
             photo = torch.zeros((num_batches, len(ms_terms), 3), dtype=torch.float32, device=g.device)
             census = torch.zeros((num_batches, len(census_terms)), dtype=torch.float32, device=g.device)
             consist = torch.zeros((num_batches, len(consist_terms), 2), dtype=torch.float32, device=g.device)
+            occl = torch.zeros((num_batches, len(occl_terms), 3), dtype=torch.float32, device=g.device)
         else:
             scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
             losses = np.zeros(num_batches, np.float64)
@@ -495,6 +584,7 @@ class ModelBase(object):
             photo = np.zeros((num_batches, len(ms_terms), 3), np.float64)
             census = np.zeros((num_batches, len(census_terms)), np.float64)
             consist = np.zeros((num_batches, len(consist_terms), 2), np.float64)
+            occl = np.zeros((num_batches, len(occl_terms), 3), np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
             if on_gpu:
@@ -508,6 +598,8 @@ class ModelBase(object):
                     census[i, j].copy_(metrics.census_loss(pred, target, max_val, 1.0, radius, eps), non_blocking=True)
                 for j, (_, flow, eps) in enumerate(consist_terms):
                     metrics.flow_consistency(flow, eps, 1.0, stats=consist[i, j])
+                for j, (_, flow, _, a1, a2, keep) in enumerate(occl_terms):
+                    metrics.flow_occlusion_mask(flow, a1, a2, keep, stats=occl[i, j])
                 if have_loss:
                     losses[i].copy_(loss, non_blocking=True)
             else:
@@ -523,10 +615,13 @@ class ModelBase(object):
                     census[i, j] = float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0])
                 for j, (_, flow, eps) in enumerate(consist_terms):
                     consist[i, j] = [float(v) for v in metrics.flow_consistency_host(flow.numpy(), eps)[2:]]
+                for j, (_, flow, _, a1, a2, keep) in enumerate(occl_terms):
+                    occl[i, j] = metrics.flow_occlusion_mask_host(flow.numpy(), a1, a2, keep)[1]
                 if have_loss:
                     losses[i] = float(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1), consist.reshape(-1)]).cpu()          # the one synchronisation
+            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1), consist.reshape(-1),
+                                occl.reshape(-1)]).cpu()          # the one synchronisation
             scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
             losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
             at = scores.size + num_batches
@@ -534,7 +629,9 @@ class ModelBase(object):
             photo = packed[at + smooth.size:at + smooth.size + photo.numel()].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
             at += smooth.size + photo.size
             census = packed[at:at + census.numel()].numpy().astype(np.float64).reshape(num_batches, len(census_terms))
-            consist = packed[at + census.size:].numpy().astype(np.float64).reshape(num_batches, len(consist_terms), 2)
+            at += census.size
+            consist = packed[at:at + consist.numel()].numpy().astype(np.float64).reshape(num_batches, len(consist_terms), 2)
+            occl = packed[at + consist.size:].numpy().astype(np.float64).reshape(num_batches, len(occl_terms), 3)
         result = {}
         if have_loss:
             result['loss'] = float(losses.mean())
@@ -553,6 +650,9 @@ class ModelBase(object):
         for j, term in enumerate(consist_terms):
             result[term[0] + '/consistency'] = float(consist[:, j, 0].mean())
             result[term[0] + '/consistency_valid'] = float(consist[:, j, 1].mean())
+        for j, term in enumerate(occl_terms):
+            for k, what in enumerate(('visible', 'occluded', 'outside')):
+                result['%s/%s' % (term[0], what)] = float(occl[:, j, k].mean())
         result['images'] = num_batches * n
         return result
 

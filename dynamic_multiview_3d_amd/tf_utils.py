@@ -8,7 +8,7 @@ conv / deconv / linear are fused into that kernel's epilogue.
 import math
 
 from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_CENSUS, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
-                    CopyConcatNode, TileNode, ResampleNode, ResamplerNode, truncated_normal_init, random_normal_init, zeros_init)
+                    CopyConcatNode, TileNode, ResampleNode, ResamplerNode, OcclusionMaskNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
 
@@ -217,6 +217,27 @@ def flow_consistency_loss(flow, eps=1e-3):
         raise ValueError("flow_consistency_loss: the flow is not differentiated (nothing to regularise)")
     eps, _ = _consist_scalars(float(eps), 1.0)
     return ScalarExpr([(1.0, LossTerm(flow, None, LOSS_CONSIST, eps=eps))])
+
+
+def occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True):
+    """The occlusion mask [B,H,W,1] of a flow field [B,H,W,2] over a pair-swapped batch (mv3d_flow_occlusion_mask;
+    metrics.flow_occlusion_mask_host states the definition): 1 where following the flow of sample n and then the partner's flow
+    there leads back to the start within |r|^2 < alpha1 (|f|^2 + |s|^2) + alpha2 (UnFlow's forward-backward test), 0 where it does
+    not, and outside_visible where the flow leaves the image and the test cannot be made.  The mask is a constant of the step
+    (requires_grad is False): use it as masked_euclidean_loss(gen, target, mask) or multiply(x, mask).  B must be even and the
+    field square."""
+    from .metrics import _consist_shape, _occlusion_scalars
+    if isinstance(flow, (_Masked, _Scaled)):
+        raise NotImplementedError("occlusion_mask of a masked or scaled operand")
+    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
+        raise ValueError("occlusion_mask: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
+    _check_usable(flow)
+    _consist_shape(flow.shape)
+    alpha1, alpha2, outside_visible = _occlusion_scalars(alpha1, alpha2, outside_visible)
+    g = current_graph()
+    mask = g.new_tensor(tuple(flow.shape[:3]) + (1,), requires_grad=False, name='occlusion_mask')
+    mask.producer = g.add(OcclusionMaskNode(flow, mask, alpha1, alpha2, outside_visible))
+    return mask
 
 
 # ------------------------------------------------------------------------------------------------ activations

@@ -31,7 +31,9 @@ one colour map per sample over all of its colour views: the TFRecord reader runs
 are handed out as augmented copies (the cycled pool stays pristine).  Validation, --evaluate and --visualize batches are never augmented;
 under data parallelism every rank draws from np.random.default_rng([augment_seed, rank]).
 With conf['pair_swap'] (pair_swap.py) every batch is conf['batch_size'] / 2 pairs and their reverses, for every input of the graph;
-conf['flow_consistency_weight'] adds the forward-backward consistency term that layout makes possible.
+conf['flow_consistency_weight'] adds the forward-backward consistency term that layout makes possible, and conf['occlusion_mask']
+takes the pixels that term's residual marks as occluded out of the head's photometric loss (`flow_visible` is then logged next to
+`training_loss`).
 """
 import argparse
 import importlib
@@ -123,7 +125,8 @@ class SyntheticData:
 
 def training_log_row(model, itr, cost, learning_rate=None):
     """The train_log.jsonl line of iteration itr: the loss, and with conf['grad_clip_norm'] / conf['grad_norm_log'] on the last
-    step's gradient norm (of the averaged gradient, before clipping) and clip scale.  Reading them synchronises, like float(cost).
+    step's gradient norm (of the averaged gradient, before clipping) and clip scale, and with conf['occlusion_mask'] on the visible
+    share of the last step's occlusion mask as `flow_visible`.  Reading them synchronises, like float(cost).
     learning_rate: the rate that iteration's update used (the host mirror, read before the update: no synchronisation), given
     whenever a schedule, a warm-up or weight decay is on."""
     row = {'itr': itr, 'training_loss': cost}
@@ -132,6 +135,8 @@ def training_log_row(model, itr, cost, learning_rate=None):
         row['grad_norm'], row['grad_clip_scale'] = norm, scale
     if learning_rate is not None:
         row['learning_rate'] = float(learning_rate)
+    if getattr(model, 'occlusion_terms', None):      # conf['occlusion_mask']: the visible share of the step's mask, so that a collapse shows
+        row['flow_visible'] = float(model.flow_visible())
     return row
 
 
@@ -163,7 +168,7 @@ def train_loop(model, conf, train_data, val_data, saver, itr_0=0, rank=0, log=No
                 row = training_log_row(model, itr, c, lr)
                 log.write(json.dumps(row) + '\n')
                 if events is not None:
-                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale', 'learning_rate'):
+                    for key in ('training_loss', 'grad_norm', 'grad_clip_scale', 'learning_rate', 'flow_visible'):
                         if key in row:
                             log_value(events, row[key], key, itr)
         if itr % VAL_INTERVAL == 0 and itr != 0:

@@ -288,7 +288,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss, mv3d_flow_consistency) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss, mv3d_flow_consistency, mv3d_warp_resample_occlusion_loss) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -510,6 +510,61 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
 size_t mv3d_flow_consistency_workspace_bytes(int N, int H, int W);
 int mv3d_flow_consistency(int N, int H, int W, const void* flow, int flow_ld, float eps, float weight, void* loss_accum, void* stats,
                           void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- occlusion masking of the appearance-flow head over pair-swapped batches ---------------------------------------------------
+ * The conventions are those of mv3d_flow_consistency, restated: flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view
+ * works), N even, H == W >= 2; the second half of the batch holds the reversed pairs of the first (pair_swap.py), the partner of
+ * sample n is m = (n + N/2) mod N; channel 0 + the ROW index is x (column), channel 1 + the COLUMN index is y (row).  For pixel
+ * (i, j) of sample n, f = flow[n,i,j,:]:
+ *   x = f0 + i,  y = f1 + j;   inside iff 0 <= x <= W-1 and 0 <= y <= H-1 (NaN and inf are not): the consistency term's strict
+ *   window, not the sampler's
+ *   s = the bilinear sample of flow[m] at (row y, column x), both channels, with the sampler's taps ff cc fc cf, its weights
+ *   w = (dx dy, (1-dx)(1-dy), dx (1-dy), (1-dx) dy) and the order ((w0 ff + w1 cc) + w2 fc) + w3 cf; a tap at index W or H occurs
+ *   only with weight 0 and reads 0
+ *   r0 = f0 + s1,  r1 = f1 + s0,  lhs = r0 r0 + r1 r1,  rhs = alpha1 ((f0 f0 + f1 f1) + (s0 s0 + s1 s1)) + alpha2
+ *   visible iff inside and lhs < rhs (a NaN on either side makes the comparison false: the pixel counts as occluded)
+ *   mask[n,i,j] = 1.0f where visible, 0.0f where inside and not visible, and outside_visible ? 1.0f : 0.0f where not inside (the
+ *   check cannot be made there: 1 keeps the plain loss on such pixels, 0 is UnFlow's choice)
+ * Every step is fp32 without contraction in the order of metrics.py flow_occlusion_mask_host at float32.  The mask has no
+ * gradient: it is a constant of the step.
+ *
+ * mv3d_flow_occlusion_mask: mask_out (optional) is [N,H,W] fp32 with pixel stride mask_ld >= 1 (a channel of a wider tensor
+ * works; the other channels are never written).  stats (optional, device, 3 floats) receives the visible, occluded and outside
+ * shares of N H W: integer counts, exact, added in a fixed order, the same bits on every run.  mask_out and stats are not both
+ * NULL.  Only a call with stats needs the workspace (16-byte aligned, mv3d_flow_occlusion_mask_workspace_bytes() bytes, 0 for a
+ * shape the entry refuses): it holds the per-tile counts.  Launches (plan labels): occl_mask, and occl_mask_stats behind it when
+ * stats is given.
+ * MV3D_E_INVAL before any launch: N < 2 or odd; H != W; H < 2 or H > 32768; N * ceil(H/32)^2 >= 2^31 or an element index that
+ * overflows; flow_ld < 2; mask_ld < 1; alpha1 not finite or < 0; alpha2 not finite or <= 0; outside_visible outside {0, 1}; flow
+ * NULL; mask_out and stats both NULL; an operand not 4-byte aligned; with stats: workspace NULL.  MV3D_E_WORKSPACE: workspace too
+ * small or not 16-byte aligned.  On any error mask_out and stats are left untouched.
+ *
+ * mv3d_warp_resample_occlusion_loss: the occlusion-aware head in one tiled pass.  The arguments of mv3d_warp_resample_loss plus
+ * alpha1, alpha2, outside_visible, an optional mask_out / mask_ld, optional stats and a workspace
+ * (mv3d_warp_resample_occlusion_loss_workspace_bytes(), always needed).  Requires Hs == H == W == Ws, N even, C <= 4.  Produces
+ *   gen (written unmasked) and warp_out (optional) with the bits of mv3d_warp_resample_fwd
+ *   the mask above (the partner-flow taps sit at the same (row y, column x) as the image taps), into mask_out when given
+ *   loss_accum[0] += weight * mean_{n,h,w} sum_c f((gen - target) * mask), f squared for kind 2 and absolute for kind 1 (the
+ *   expressions of mv3d_pixel_loss_strided with a mask); = instead of += when mv3d_loss_overwrite_next() is pending on the calling
+ *   thread (the flag is consumed; a recorded call keeps what it saw).  The fp32 terms are added in double per tile in a fixed
+ *   order, the tiles in index order by a last launch: no floating-point atomics, the same bits on every run
+ *   dflow (optional, pixel stride dflow_ld >= 2) = d(weight * loss) / dflow with the mask held constant: bit for bit what
+ *   mv3d_flow_occlusion_mask, mv3d_warp_resample_fwd, mv3d_pixel_loss_strided(mask) and mv3d_warp_resample_bwd give in a row
+ *   stats (optional, 3 floats) as above.
+ * Launches (plan labels): occl_head_tile, occl_head_final.
+ * MV3D_E_INVAL before any launch: the shape errors above; Hs != H or Ws != W; C outside 1..4; flow_ld < 2; target_ld < C; dflow
+ * with dflow_ld < 2; mask_out with mask_ld < 1; kind outside {1, 2}; weight not finite; the alpha and outside_visible errors
+ * above; src, flow, target, gen or loss_accum NULL; workspace NULL; an operand not 4-byte aligned.  MV3D_E_WORKSPACE: workspace
+ * too small or not 16-byte aligned.  On any error loss_accum, stats, mask_out, gen, warp_out and dflow are left untouched and a
+ * pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_flow_occlusion_mask_workspace_bytes(int N, int H, int W);
+int mv3d_flow_occlusion_mask(int N, int H, int W, const void* flow, int flow_ld, float alpha1, float alpha2, int outside_visible,
+                             void* mask_out, int mask_ld, void* stats, void* workspace, size_t workspace_bytes, void* stream);
+size_t mv3d_warp_resample_occlusion_loss_workspace_bytes(int N, int H, int W);
+int mv3d_warp_resample_occlusion_loss(int N, int H, int W, int Hs, int Ws, int C, const void* src, const void* flow, int flow_ld,
+                                      const void* target, int target_ld, int kind, float weight, float alpha1, float alpha2,
+                                      int outside_visible, void* warp_out, void* gen, void* dflow, int dflow_ld, void* mask_out,
+                                      int mask_ld, void* loss_accum, void* stats, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Adam: tf.train.AdamOptimizer ApplyAdam (appearance_flow_model.py:77) -------
  *   alpha = lr*sqrt(1-beta2_power)/(1-beta1_power);  m += (g-m)(1-b1);  v += (g*g-v)(1-b2);
