@@ -299,30 +299,149 @@ class ScalarExpr:
 
 
 LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CENSUS, LOSS_CONSIST = 1, 2, 3, 4, 5, 6, 7
-FLOW_TERMS = (LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST)     # terms on a flow, usually an intermediate tensor: their gradient launch can be deferred
 
 
 class LossTerm:
-    """One term of the loss on the differentiated tensor a against b.  kind LOSS_L1 / LOSS_L2: the pixel losses (mv3d_pixel_loss*),
-    with an optional one-channel mask and a scale on b.  kind LOSS_SSIM: 1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss);
-    no mask, no scale.  kind LOSS_CENSUS: the soft census loss over (2 radius + 1)^2 patches at dynamic range max_val with
-    Charbonnier eps (mv3d_census_loss); no mask, no scale.  kind LOSS_SMOOTH: the edge-aware smoothness of the flow a
-    (mv3d_flow_smoothness) with b the guide image or None, edge parameter edge_alpha and Charbonnier eps; a is usually an INTERMEDIATE tensor whose gradient also arrives from its
-    consumer (Graph._emit_losses / _smooth_before / _smooth_after merge the two).  kind LOSS_MULTISCALE: the multi-scale
-    photometric loss (mv3d_multiscale_warp_loss) of the flow a, merged the same way, that warps the third operand `src` onto the
-    target b over `levels` pyramid levels with per-level weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2);
-    neither image is differentiated.  kind LOSS_CONSIST: the forward-backward consistency (mv3d_flow_consistency) of the flow a
-    over a pair-swapped batch with Charbonnier eps, merged the same way; b is None.  `ws` is an SSIM, census, smoothness,
-    multi-scale or consistency term's own workspace, allocated by
-    Graph.compile(); a multi-scale term's also holds the pyramids its forward call builds and its reverse call reuses."""
+    """One term of the loss on the differentiated tensor a against b.  A class states its `kind` (LOSS_*), its `order` (the terms
+    of a step are launched in this order: Graph._emit_losses) and `on_flow`: a term on a flow, usually an INTERMEDIATE tensor whose
+    gradient also arrives from its consumer, so that its gradient launch can be deferred into the reverse plans
+    (Graph._flow_term_before / _flow_term_after merge the two).  `ws` is the term's own workspace, allocated by Graph.compile()."""
+    kind, order, on_flow = None, None, False
 
-    def __init__(self, a, b, kind, mask=None, b_scale=1.0, max_val=1.0, edge_alpha=0.0, eps=1e-3, src=None, levels=0,
-                 level_weights=(), pixel_kind=LOSS_L2, radius=3):
-        self.a, self.b, self.kind, self.mask, self.b_scale = a, b, kind, mask, float(b_scale)
+    def __init__(self, a, b, mask=None):
+        self.a, self.b, self.mask, self.ws = a, b, mask, None
+
+    def workspace_bytes(self, lib):
+        """Bytes of the workspace this term needs (ValueError where the kernel does not take its operands), or None for none."""
+        return None
+
+    @staticmethod
+    def _nonzero(nbytes, message):
+        """The workspace size the library answers, or ValueError(message) where it answers 0."""
+        if not int(nbytes):
+            raise ValueError(message)
+        return int(nbytes)
+
+    def launch(self, g, w, value, grad, accumulate):
+        """Record the term's library call at weight w: the value into the loss word and / or the gradient stored into (or, with
+        accumulate, added onto) a's gradient buffer."""
+        raise NotImplementedError
+
+
+class PixelTerm(LossTerm):
+    """kind LOSS_L1 / LOSS_L2: the pixel losses (mv3d_pixel_loss*), with an optional one-channel mask and a scale on b; no workspace."""
+    order = 0
+
+    def __init__(self, a, b, kind, mask=None, b_scale=1.0):
+        LossTerm.__init__(self, a, b, mask)
+        self.kind, self.b_scale = kind, float(b_scale)
+
+    def launch(self, g, w, value, grad, accumulate):
+        a, b, m = self.a, self.b, self.mask
+        g.lib.pixel_loss_strided(a.rows, a.C, a.ptr, a.ld, b.ptr, b.ld, self.b_scale, m.ptr if m is not None else None,
+                                 m.ld if m is not None else 1, self.kind, float(w), g.loss_buf.data_ptr(), a.grad_ptr if grad else None, a.ld, g.stream)
+
+
+class SsimTerm(LossTerm):
+    """1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss).  The workspace holds the per-tile sums (not the shared scratch: the
+    term's two launches must find it untouched whatever runs beside them)."""
+    kind, order = LOSS_SSIM, 1
+
+    def __init__(self, a, b, max_val=1.0):
+        LossTerm.__init__(self, a, b)
         self.max_val = float(max_val)
-        self.edge_alpha, self.eps, self.radius = float(edge_alpha), float(eps), int(radius)
+
+    def workspace_bytes(self, lib):
+        return self._nonzero(lib.ssim_loss_workspace_bytes(*self.a.shape),
+                             "ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (self.a.shape,))
+
+    def launch(self, g, w, value, grad, accumulate):
+        a, b = self.a, self.b
+        g.lib.ssim_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.max_val, float(w), g.loss_buf.data_ptr(),
+                        a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+
+
+class CensusTerm(LossTerm):
+    """The soft census loss over (2 radius + 1)^2 patches at dynamic range max_val with Charbonnier eps (mv3d_census_loss)."""
+    kind, order = LOSS_CENSUS, 2
+
+    def __init__(self, a, b, max_val=1.0, radius=3, eps=1e-3):
+        LossTerm.__init__(self, a, b)
+        self.max_val, self.radius, self.eps = float(max_val), int(radius), float(eps)
+
+    def workspace_bytes(self, lib):
+        return self._nonzero(lib.census_loss_workspace_bytes(*self.a.shape, self.radius),
+                             "census_loss: operands of shape %s at radius %d are outside what mv3d_census_loss takes" % (self.a.shape, self.radius))
+
+    def launch(self, g, w, value, grad, accumulate):
+        a, b = self.a, self.b
+        g.lib.census_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.radius, self.max_val, self.eps, float(w), g.loss_buf.data_ptr(),
+                          a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+
+
+class SmoothTerm(LossTerm):
+    """The edge-aware smoothness of the flow a (mv3d_flow_smoothness) with b the guide image or None, edge parameter edge_alpha
+    and Charbonnier eps.  The workspace holds 2 sums per tile."""
+    kind, order, on_flow = LOSS_SMOOTH, 3, True
+
+    def __init__(self, a, b, edge_alpha=0.0, eps=1e-3):
+        LossTerm.__init__(self, a, b)
+        self.edge_alpha, self.eps = float(edge_alpha), float(eps)
+
+    def workspace_bytes(self, lib):
+        return self._nonzero(lib.flow_smoothness_workspace_bytes(*self.a.shape[:3]),
+                             "flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (self.a.shape,))
+
+    def launch(self, g, w, value, grad, accumulate):
+        a, b = self.a, self.b
+        gp, gc, gld = (b.ptr, b.C, b.ld) if b is not None else (None, 0, 0)
+        g.lib.flow_smoothness(*a.shape[:3], a.ptr, a.ld, gp, gc, gld, self.edge_alpha, self.eps, float(w), g.loss_buf.data_ptr() if value else None,
+                              a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+
+
+class MultiscaleTerm(LossTerm):
+    """The multi-scale photometric loss (mv3d_multiscale_warp_loss) of the flow a, which warps `src` onto the target b over `levels`
+    pyramid levels with weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2); neither image is differentiated.
+    The workspace holds the tile sums and both pyramids: a call without the value is the reverse-pass call, which reuses them."""
+    kind, order, on_flow = LOSS_MULTISCALE, 4, True
+
+    def __init__(self, a, b, src, levels, level_weights, pixel_kind=LOSS_L2):
+        LossTerm.__init__(self, a, b)
         self.src, self.levels, self.level_weights, self.pixel_kind = src, int(levels), tuple(float(v) for v in level_weights), pixel_kind
-        self.ws = None
+
+    def workspace_bytes(self, lib):
+        return self._nonzero(lib.multiscale_warp_loss_workspace_bytes(*self.a.shape[:3], *self.src.shape[1:], self.levels),
+                             "multiscale_photometric_loss: a flow of shape %s over a source of shape %s at %d levels is outside "
+                             "what mv3d_multiscale_warp_loss takes" % (self.a.shape, self.src.shape, self.levels))
+
+    def launch(self, g, w, value, grad, accumulate):
+        a, b, s = self.a, self.b, self.src
+        weights = (C.c_float * self.levels)(*[float(w) * v for v in self.level_weights])
+        g.lib.multiscale_warp_loss(*a.shape[:3], s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, self.levels, weights,
+                                   self.pixel_kind, g.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None, a.ld,
+                                   1 if (grad and accumulate) else 0, 0 if value else 1, self.ws.data_ptr(), self.ws.numel(), g.stream)
+
+
+class ConsistTerm(LossTerm):
+    """The forward-backward consistency (mv3d_flow_consistency) of the flow a over a pair-swapped batch with Charbonnier eps; b is
+    None.  The workspace holds the int64 scatter plane, the float plane of the gathered part and the tile sums."""
+    kind, order, on_flow = LOSS_CONSIST, 5, True
+
+    def __init__(self, a, eps=1e-3):
+        LossTerm.__init__(self, a, None)
+        self.eps = float(eps)
+
+    def workspace_bytes(self, lib):
+        return self._nonzero(lib.flow_consistency_workspace_bytes(*self.a.shape[:3]),
+                             "flow_consistency_loss: a flow of shape %s is outside what mv3d_flow_consistency takes" % (self.a.shape,))
+
+    def launch(self, g, w, value, grad, accumulate):
+        a = self.a
+        g.lib.flow_consistency(*a.shape[:3], a.ptr, a.ld, self.eps, float(w), g.loss_buf.data_ptr() if value else None, None,
+                               a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+
+
+FLOW_TERMS = tuple(c.kind for c in LossTerm.__subclasses__() if c.on_flow)      # (LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST)
 
 
 # =============================================================================================== nodes
@@ -756,7 +875,7 @@ class Graph:
         self.plan_bwd_fused = None
         self.opt_state = None
         self.plan_fwd = self.plan_bwd = None
-        self._smooth_deferred = []      # [(weight, LossTerm)]: smoothness terms whose gradient launch goes into the reverse plans
+        self._flow_terms_deferred = []      # [(weight, LossTerm)]: terms on a flow whose gradient launch goes into the reverse plans
         # the update rule (model_base: AdamOptimizer, MomentumOptimizer, GradientDescentOptimizer); slots and state follow it
         self.optimizer = 'adam'
         self.momentum, self.use_nesterov = 0.0, False
@@ -933,7 +1052,7 @@ class Graph:
             if len(uses) != 1:
                 continue
             w, t = uses[0]
-            if t.kind in (LOSS_SSIM, LOSS_CENSUS):
+            if not isinstance(t, PixelTerm):
                 continue            # the SSIM and census losses need gen and write their gradient in HBM: they never fuse
             if t.a is not gen or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
                 continue
@@ -1014,103 +1133,61 @@ class Graph:
     def _emit_losses(self, with_grad):
         if self.loss_expr is None:
             return
-        # A pixel loss stores its gradient, the SSIM and census losses can add to one: the pixel terms go first, then the SSIM
-        # terms, then the census terms, and each of the latter accumulates when an earlier term of this step has written the
-        # gradient of the same tensor (L2 + SSIM + census on one prediction).
-        # A smoothness term sits on an intermediate tensor (the flow).  Where the forward plan has already stored that tensor's
-        # gradient (the fused head, mv3d_warp_resample_loss), one launch gives the value and adds the gradient.  Otherwise only the
-        # value is recorded here and the gradient launch is deferred to the reverse plan (_smooth_before / _smooth_after).
+        # A pixel loss stores its gradient, the SSIM and census losses can add to one: the terms go in their classes' `order`, and an
+        # SSIM or census term accumulates when an earlier term of this step has written the gradient of the same tensor (L2 + SSIM +
+        # census on one prediction).  A term on a flow sits on an intermediate tensor.  Where the forward plan has already stored that
+        # tensor's gradient (the fused head, mv3d_warp_resample_loss), one launch gives the value and adds the gradient.  Otherwise
+        # only the value is recorded here and the gradient launch is deferred to the reverse plan (_flow_term_before / _after).
         written = set()             # gradient addresses written by the terms so far
-        # A multi-scale photometric term sits on the flow as well and is placed by the same rule, behind the smoothness terms.
-        # A forward-backward consistency term does too, behind the multi-scale terms.
-        order = lambda k: {LOSS_SSIM: 1, LOSS_CENSUS: 2, LOSS_SMOOTH: 3, LOSS_MULTISCALE: 4, LOSS_CONSIST: 5}.get(k, 0)
-        terms = sorted(self.loss_expr.terms, key=lambda wt: order(wt[1].kind))      # stable: the terms of a kind keep their order
-        self._smooth_deferred = []
-        for w, term in terms:
+        self._flow_terms_deferred = []
+        for w, term in sorted(self.loss_expr.terms, key=lambda wt: wt[1].order):       # stable: the terms of a kind keep their order
             if id(term) in self.fused_terms:
                 continue
-            a, b, m = term.a, term.b, term.mask
-            if term.kind in FLOW_TERMS:
+            a, b = term.a, term.b
+            if term.on_flow:
                 both = with_grad and a.requires_grad and a.grad_written
-                self._smooth_launch(w, term, value=True, grad=both, accumulate=both)
+                self._flow_term_launch(w, term, value=True, grad=both, accumulate=both)
                 if with_grad and a.requires_grad and not both:
-                    self._smooth_deferred.append((w, term))
+                    self._flow_terms_deferred.append((w, term))
                 continue
             if a.C != b.C or a.rows != b.rows:
                 raise ValueError("loss operands of different shapes")
-            grad = a.grad_ptr if (with_grad and a.requires_grad) else None
-            if term.kind == LOSS_SSIM:
-                n, h, wd, c = a.shape
-                self.lib.ssim_loss(n, h, wd, c, a.ptr, a.ld, b.ptr, b.ld, term.max_val, float(w), self.loss_buf.data_ptr(), grad, a.ld,
-                                   1 if grad in written else 0, term.ws.data_ptr(), term.ws.numel(), self.stream)
-            elif term.kind == LOSS_CENSUS:
-                n, h, wd, c = a.shape
-                self.lib.census_loss(n, h, wd, c, a.ptr, a.ld, b.ptr, b.ld, term.radius, term.max_val, term.eps, float(w),
-                                     self.loss_buf.data_ptr(), grad, a.ld, 1 if grad in written else 0, term.ws.data_ptr(),
-                                     term.ws.numel(), self.stream)
-            else:
-                self.lib.pixel_loss_strided(a.rows, a.C, a.ptr, a.ld, b.ptr, b.ld, term.b_scale,
-                                            m.ptr if m is not None else None, m.ld if m is not None else 1,
-                                            term.kind, float(w), self.loss_buf.data_ptr(), grad, a.ld, self.stream)
-            if grad is not None:
-                written.add(grad)
+            grad = with_grad and a.requires_grad
+            term.launch(self, w, value=True, grad=grad, accumulate=grad and a.grad_ptr in written)
+            if grad:
+                written.add(a.grad_ptr)
                 _note_grad_written(a, False)
 
-    def _smooth_launch(self, w, term, value, grad, accumulate):
-        """One call of a term on a flow (mv3d_flow_smoothness for LOSS_SMOOTH, mv3d_multiscale_warp_loss for LOSS_MULTISCALE,
-        mv3d_flow_consistency for LOSS_CONSIST): the
-        value into the loss word and / or the gradient stored into or added onto the flow's gradient buffer.  A multi-scale call
-        without the value is the reverse-pass call: the value call of this step has left the pyramids in the term's workspace."""
-        a, b = term.a, term.b
-        if grad and accumulate and a.grad_masked:
+    def _flow_term_launch(self, w, term, value, grad, accumulate):
+        """One call of a term on a flow (LossTerm.launch), refused where the add would land on a masked gradient."""
+        if grad and accumulate and term.a.grad_masked:
             raise NotImplementedError("a loss term on a flow whose gradient buffer already holds d/d(pre-activation)")
-        n, h, wd, _ = a.shape
-        if term.kind == LOSS_MULTISCALE:
-            s = term.src
-            weights = (C.c_float * term.levels)(*[float(w) * v for v in term.level_weights])
-            self.lib.multiscale_warp_loss(n, h, wd, s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, term.levels, weights,
-                                          term.pixel_kind, self.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None,
-                                          a.ld, 1 if (grad and accumulate) else 0, 0 if value else 1, term.ws.data_ptr(), term.ws.numel(),
-                                          self.stream)
-            if grad:
-                _note_grad_written(a, False)
-            return
-        if term.kind == LOSS_CONSIST:
-            self.lib.flow_consistency(n, h, wd, a.ptr, a.ld, term.eps, float(w), self.loss_buf.data_ptr() if value else None, None,
-                                      a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, term.ws.data_ptr(),
-                                      term.ws.numel(), self.stream)
-            if grad:
-                _note_grad_written(a, False)
-            return
-        self.lib.flow_smoothness(n, h, wd, a.ptr, a.ld, b.ptr if b is not None else None, b.C if b is not None else 0,
-                                 b.ld if b is not None else 0, term.edge_alpha, term.eps, float(w),
-                                 self.loss_buf.data_ptr() if value else None, a.grad_ptr if grad else None, a.ld,
-                                 1 if (grad and accumulate) else 0, term.ws.data_ptr(), term.ws.numel(), self.stream)
+        term.launch(self, w, value, grad, accumulate)
         if grad:
-            _note_grad_written(a, False)
+            _note_grad_written(term.a, False)
 
-    def _smooth_before(self, n, pending):
-        """Reverse plan, in front of node n's backward: a deferred smoothness term on a tensor n produces whose gradient nobody
+    def _flow_term_before(self, n, pending):
+        """Reverse plan, in front of node n's backward: a deferred term on a tensor n produces whose gradient nobody
         has written STORES it (the term is that tensor's only source of gradient); the producer's backward then runs from it.
         Store or add is decided per term at its launch: of several terms on one tensor the first stores and the others add."""
         for wt in [wt for wt in pending if wt[1].a.producer is n]:
-            self._smooth_launch(wt[0], wt[1], value=False, grad=True, accumulate=wt[1].a.grad_written)
+            self._flow_term_launch(wt[0], wt[1], value=False, grad=True, accumulate=wt[1].a.grad_written)
             pending.remove(wt)
 
-    def _smooth_after(self, pending):
-        """Reverse plan, behind a node's backward: a deferred smoothness term whose tensor has just received its gradient from
+    def _flow_term_after(self, pending):
+        """Reverse plan, behind a node's backward: a deferred term whose tensor has just received its gradient from
         a consumer (the resampler's backward) ADDS its own, one fp32 addition per element, before the tensor's producer runs."""
         for wt in [wt for wt in pending if wt[1].a.grad_written]:
-            self._smooth_launch(wt[0], wt[1], value=False, grad=True, accumulate=True)
+            self._flow_term_launch(wt[0], wt[1], value=False, grad=True, accumulate=True)
             pending.remove(wt)
 
     def _backward_node(self, n, pending):
-        self._smooth_before(n, pending)
+        self._flow_term_before(n, pending)
         n.backward(self)
-        self._smooth_after(pending)
+        self._flow_term_after(pending)
 
     @staticmethod
-    def _smooth_all_placed(pending):
+    def _flow_terms_all_placed(pending):
         """End of a reverse recording: a deferred term that found no place is an error, not a silently missing gradient."""
         if pending:
             raise RuntimeError("a loss term on a flow: the reverse pass has no place for the gradient of %d term(s): no node of "
@@ -1123,39 +1200,13 @@ class Graph:
         lib = self.lib
         for t in self.tensors:
             t.grad_written = t.grad_masked = False
-        self._smooth_deferred = []
+        self._flow_terms_deferred = []
         self._bind_prepared_filters()
         self._fuse_resample_losses()
-        # every SSIM term keeps its per-tile sums in a workspace of its own (not the shared scratch: the term's two launches must
-        # find it untouched whatever runs beside them)
+        # every term that needs a workspace keeps one of its own (not the shared scratch: see SsimTerm)
         for _, term in (self.loss_expr.terms if self.loss_expr is not None else ()):
-            if term.kind == LOSS_SSIM and term.ws is None:
-                nbytes = int(lib.ssim_loss_workspace_bytes(*term.a.shape))
-                if not nbytes:
-                    raise ValueError("ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (term.a.shape,))
-                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            if term.kind == LOSS_CENSUS and term.ws is None:     # likewise for a census term
-                nbytes = int(lib.census_loss_workspace_bytes(*term.a.shape, term.radius))
-                if not nbytes:
-                    raise ValueError("census_loss: operands of shape %s at radius %d are outside what mv3d_census_loss takes"
-                                     % (term.a.shape, term.radius))
-                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            if term.kind == LOSS_SMOOTH and term.ws is None:     # likewise for a smoothness term (2 sums per tile)
-                nbytes = int(lib.flow_smoothness_workspace_bytes(*term.a.shape[:3]))
-                if not nbytes:
-                    raise ValueError("flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (term.a.shape,))
-                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            if term.kind == LOSS_CONSIST and term.ws is None:    # the int64 scatter plane, the float plane of the gathered part and the tile sums
-                nbytes = int(lib.flow_consistency_workspace_bytes(*term.a.shape[:3]))
-                if not nbytes:
-                    raise ValueError("flow_consistency_loss: a flow of shape %s is outside what mv3d_flow_consistency takes" % (term.a.shape,))
-                term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            if term.kind == LOSS_MULTISCALE and term.ws is None:     # the tile sums and the pyramids of src and target
-                s = term.src
-                nbytes = int(lib.multiscale_warp_loss_workspace_bytes(*term.a.shape[:3], s.shape[1], s.shape[2], s.C, term.levels))
-                if not nbytes:
-                    raise ValueError("multiscale_photometric_loss: a flow of shape %s over a source of shape %s at %d levels is outside "
-                                     "what mv3d_multiscale_warp_loss takes" % (term.a.shape, s.shape, term.levels))
+            nbytes = term.workspace_bytes(lib) if term.ws is None else None
+            if nbytes is not None:
                 term.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._find_fc_chains()
         self.plan_fwd = lib.plan_create()
@@ -1184,7 +1235,7 @@ class Graph:
             suffix = len(order)         # variables[suffix:] are complete
             cut_hi = self.flat_size
             gate = 0
-            pending = list(self._smooth_deferred)
+            pending = list(self._flow_terms_deferred)
             for n in reversed(self.nodes):
                 self._backward_node(n, pending)
                 if isinstance(n, LinearNode):
@@ -1209,7 +1260,7 @@ class Graph:
                 if cut_hi - lo >= self.bucket_elems or boundary:
                     self.grad_buckets.append((lib.plan_size(self.plan_bwd), lo, cut_hi))
                     cut_hi = lo
-            self._smooth_all_placed(pending)
+            self._flow_terms_all_placed(pending)
         finally:
             lib.plan_end()
         nbwd = lib.plan_size(self.plan_bwd)
@@ -1264,7 +1315,7 @@ class Graph:
                 self._fin_pending, self._fin_vars, self._fin_done, self._fin_tables = 0, [], set(), []
             lib.plan_begin(plan)
             self._fusing = True
-            pending = list(self._smooth_deferred)
+            pending = list(self._flow_terms_deferred)
             try:
                 for n in reversed(self.nodes):
                     self._backward_node(n, pending)
@@ -1276,7 +1327,7 @@ class Graph:
                         if self._fin_pending >= self.finalize_chunk_bytes:
                             self._finalize_commit()
                             lib.grad_finalize_begin()
-                self._smooth_all_placed(pending)
+                self._flow_terms_all_placed(pending)
                 for n in self._fused_nodes:         # the fused fc optimiser goes behind the whole reverse pass
                     n.record_fused_update(self)
                 if self._finalizing and self._fused_vars:

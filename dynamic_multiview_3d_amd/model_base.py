@@ -333,6 +333,10 @@ class ModelBase(object):
         if occlusion_from_conf(self.conf) is not None and not self.supports_occlusion_mask:
             raise ValueError("%s does not support conf['occlusion_mask']" % type(self).__name__)
 
+    def _note_term(self, attr, entry):
+        """One more entry of a per-term list that evaluate() reports from (_report); the list exists only once a term was added."""
+        self.__dict__.setdefault(attr, []).append(entry)
+
     def head_loss(self, gen, target, flow, name='flow'):
         """The photometric term of an appearance-flow head: euclidean_loss(gen, target), exactly the reference's, when
         conf['occlusion_mask'] is absent, None or False (the graph then records what it recorded without the key); with the key on,
@@ -344,9 +348,7 @@ class ModelBase(object):
         if occl is None:
             return euclidean_loss(gen, target)
         mask = occlusion_mask(flow, *occl)
-        if not hasattr(self, 'occlusion_terms'):
-            self.occlusion_terms = []           # [(name, flow, mask tensor, alpha1, alpha2, outside_visible)]
-        self.occlusion_terms.append((name, flow, mask) + tuple(occl))
+        self._note_term('occlusion_terms', (name, flow, mask) + tuple(occl))      # (name, flow, mask tensor, alpha1, alpha2, outside_visible)
         return masked_euclidean_loss(gen, target, mask)
 
     def occlusion_mask(self, name='flow'):
@@ -378,9 +380,7 @@ class ModelBase(object):
         w, eps = flow_consistency_from_conf(self.conf)
         if w == 0:
             return 0
-        if not hasattr(self, 'consistency_terms'):
-            self.consistency_terms = []         # [(name, flow, eps)]
-        self.consistency_terms.append((name, flow, eps))
+        self._note_term('consistency_terms', (name, flow, eps))
         return flow_consistency_loss(flow, eps) * w
 
     def multiscale_term(self, flow, src, target, name='flow'):
@@ -392,9 +392,7 @@ class ModelBase(object):
         levels, weights, kind = multiscale_loss_from_conf(self.conf)
         if levels == 0:
             return 0
-        if not hasattr(self, 'multiscale_terms'):
-            self.multiscale_terms = []          # [(name, flow, src, target, levels, kind)]
-        self.multiscale_terms.append((name, flow, src, target, levels, kind))
+        self._note_term('multiscale_terms', (name, flow, src, target, levels, kind))
         return multiscale_photometric_loss(flow, src, target, levels, weights, kind)
 
     def flow_smoothness_term(self, flow, guide, name='flow'):
@@ -408,10 +406,15 @@ class ModelBase(object):
             return 0
         if alpha == 0:
             guide = None
-        if not hasattr(self, 'smoothness_terms'):
-            self.smoothness_terms = []          # [(name, flow, guide or None, edge_alpha, eps)]
-        self.smoothness_terms.append((name, flow, guide, alpha, eps))
+        self._note_term('smoothness_terms', (name, flow, guide, alpha, eps))       # (name, flow, guide or None, edge_alpha, eps)
         return flow_smoothness_loss(flow, guide, alpha, eps) * w
+
+    def _eval_pair(self, op, pred, target):
+        """(name, max_val) of this model's eval_pairs() entry for the pair."""
+        for name, p, t, max_val in self.eval_pairs():
+            if p is pred and t is target:
+                return name, max_val
+        raise RuntimeError("%s: eval_pairs() of %s has no entry for this pair" % (op, type(self).__name__))
 
     def ssim_term(self, pred, target):
         """conf['ssim_loss_weight'] * ssim_loss(pred, target, max_val) with max_val from this model's eval_pairs() entry of the
@@ -420,10 +423,7 @@ class ModelBase(object):
         w = ssim_weight_from_conf(self.conf)
         if w == 0:
             return 0
-        for _, p, t, max_val in self.eval_pairs():
-            if p is pred and t is target:
-                return ssim_loss(pred, target, max_val) * w
-        raise RuntimeError("ssim_term: eval_pairs() of %s has no entry for this pair" % type(self).__name__)
+        return ssim_loss(pred, target, self._eval_pair('ssim_term', pred, target)[1]) * w
 
     def census_term(self, pred, target):
         """conf['census_loss_weight'] * census_loss(pred, target, max_val, radius, eps) with max_val from this model's eval_pairs()
@@ -434,14 +434,10 @@ class ModelBase(object):
         w, radius, eps = census_from_conf(self.conf)
         if w == 0:
             return 0
-        for name, p, t, max_val in self.eval_pairs():
-            if p is pred and t is target:
-                term = census_loss(pred, target, max_val, radius, eps) * w
-                if not hasattr(self, 'census_terms'):
-                    self.census_terms = []          # [(pair name, pred, target, max_val, radius, eps)]
-                self.census_terms.append((name, pred, target, max_val, radius, eps))
-                return term
-        raise RuntimeError("census_term: eval_pairs() of %s has no entry for this pair" % type(self).__name__)
+        name, max_val = self._eval_pair('census_term', pred, target)
+        term = census_loss(pred, target, max_val, radius, eps) * w
+        self._note_term('census_terms', (name, pred, target, max_val, radius, eps))        # name: the pair's
+        return term
 
     def _make_graph(self, device, seed):
         self._check_conf()
@@ -534,25 +530,12 @@ class ModelBase(object):
         """The quantitative counterpart of mv3d.test() (mv3d/nobg_dm.py:117-149): forward(**data.next()) num_batches times
         (19 = the reference's test_iter), the loss averaged over the batches (:143-145), and per-image L1 / PSNR / SSIM of every
         eval_pairs() entry averaged over the images (metrics.py; PSNR is averaged per image, an image with mse == 0 makes it inf).
-
-        On the GPU every batch appends its [N,3] metrics (mv3d_image_metrics) and its loss to device buffers and the host
-        synchronises once, after the last batch.  On a CPU graph the numpy form (image_metrics_host) scores each batch.
+        Every loss switch that is on adds its unweighted figures, averaged over the batches, under the keys its *_term() method or
+        head_loss() names: _report() below is the table of everything reported.
+        On the GPU every batch writes its figures (the device kernels') into its row of one device buffer and the host synchronises
+        once, after the last batch.  On a CPU graph the numpy forms score each batch.
         Only forward passes run: parameters, optimiser slots and the step counter are left as they were.
-        With conf['flow_smoothness_weight'] > 0 every flow head's unweighted smoothness S (mv3d_flow_smoothness; numpy form on a
-        CPU graph), averaged over the batches, is reported as '<head>/smoothness' ('flow/smoothness' for the single-head models).
-        With conf['multiscale_loss_levels'] on, every flow head's unweighted level terms T_l (the level_values of
-        mv3d_multiscale_warp_loss; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/photo_x2',
-        '<head>/photo_x4' and '<head>/photo_x8'.
-        With conf['flow_consistency_weight'] > 0 the unweighted forward-backward consistency C of the flow head and its share of
-        valid pixels (the stats of mv3d_flow_consistency; numpy form on a CPU graph), averaged over the batches, are reported as
-        '<head>/consistency' and '<head>/consistency_valid'.
-        With conf['census_loss_weight'] > 0 the unweighted census term of every pair that carries one (mv3d_census_loss; numpy
-        form on a CPU graph), averaged over the batches, is reported as '<pair>/census'.
-        With conf['occlusion_mask'] on, the visible, occluded and outside shares of the head's occlusion mask (the stats of
-        mv3d_flow_occlusion_mask; numpy form on a CPU graph), averaged over the batches, are reported as '<head>/visible',
-        '<head>/occluded' and '<head>/outside'.
         Returns {'loss': .., '<pair>/l1': .., '<pair>/psnr': .., '<pair>/ssim': .., 'images': count}."""
-        from . import metrics
         g = self.graph
         num_batches = int(num_batches)
         if num_batches < 1:
@@ -561,100 +544,71 @@ class ModelBase(object):
         if not pairs:
             raise RuntimeError("evaluate: the built graph has no prediction / target pair")
         n = pairs[0][1].shape[0]
-        have_loss = g.loss_expr is not None
+        report = self._report(pairs, n)
         on_gpu = g.device.type == 'cuda'
-        smooth_terms = getattr(self, 'smoothness_terms', [])
-        ms_terms = getattr(self, 'multiscale_terms', [])
-        ms_kind = {'l1': 1, 'l2': 2}
-        census_terms = getattr(self, 'census_terms', [])
-        consist_terms = getattr(self, 'consistency_terms', [])
-        occl_terms = getattr(self, 'occlusion_terms', [])
-        if on_gpu:
-            scores = torch.empty((num_batches, len(pairs), n, 3), dtype=torch.float32, device=g.device)
-            losses = torch.zeros(num_batches, dtype=torch.float32, device=g.device)
-            smooth = torch.zeros((num_batches, len(smooth_terms)), dtype=torch.float32, device=g.device)
-            photo = torch.zeros((num_batches, len(ms_terms), 3), dtype=torch.float32, device=g.device)
-            census = torch.zeros((num_batches, len(census_terms)), dtype=torch.float32, device=g.device)
-            consist = torch.zeros((num_batches, len(consist_terms), 2), dtype=torch.float32, device=g.device)
-            occl = torch.zeros((num_batches, len(occl_terms), 3), dtype=torch.float32, device=g.device)
-        else:
-            scores = np.empty((num_batches, len(pairs), n, 3), np.float64)
-            losses = np.zeros(num_batches, np.float64)
-            smooth = np.zeros((num_batches, len(smooth_terms)), np.float64)
-            photo = np.zeros((num_batches, len(ms_terms), 3), np.float64)
-            census = np.zeros((num_batches, len(census_terms)), np.float64)
-            consist = np.zeros((num_batches, len(consist_terms), 2), np.float64)
-            occl = np.zeros((num_batches, len(occl_terms), 3), np.float64)
+        starts = np.cumsum([0] + [e[0] for e in report])        # entry k owns columns starts[k] .. starts[k + 1] of every batch's row
+        shape = (num_batches, int(starts[-1]))
+        buf = torch.empty(shape, dtype=torch.float32, device=g.device) if on_gpu else np.empty(shape, np.float64)
         for i in range(num_batches):
             loss = self.forward(**data.next())
-            if on_gpu:
-                for j, (_, pred, target, max_val) in enumerate(pairs):
-                    metrics.image_metrics(pred, target, max_val, out=scores[i, j])
-                for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
-                    smooth[i, j].copy_(metrics.flow_smoothness(flow, guide, alpha, eps), non_blocking=True)
-                for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
-                    photo[i, j, :levels].copy_(metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1], non_blocking=True)
-                for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
-                    census[i, j].copy_(metrics.census_loss(pred, target, max_val, 1.0, radius, eps), non_blocking=True)
-                for j, (_, flow, eps) in enumerate(consist_terms):
-                    metrics.flow_consistency(flow, eps, 1.0, stats=consist[i, j])
-                for j, (_, flow, _, a1, a2, keep) in enumerate(occl_terms):
-                    metrics.flow_occlusion_mask(flow, a1, a2, keep, stats=occl[i, j])
-                if have_loss:
-                    losses[i].copy_(loss, non_blocking=True)
-            else:
-                for j, (_, pred, target, max_val) in enumerate(pairs):
-                    scores[i, j] = metrics.image_metrics_host(pred.numpy(), target.numpy(), max_val)
-                for j, (_, flow, guide, alpha, eps) in enumerate(smooth_terms):
-                    smooth[i, j] = float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None,
-                                                                      alpha, eps)[0])
-                for j, (_, flow, src, target, levels, kind) in enumerate(ms_terms):
-                    photo[i, j, :levels] = metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None,
-                                                                             ms_kind[kind])[2]
-                for j, (_, pred, target, max_val, radius, eps) in enumerate(census_terms):
-                    census[i, j] = float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0])
-                for j, (_, flow, eps) in enumerate(consist_terms):
-                    consist[i, j] = [float(v) for v in metrics.flow_consistency_host(flow.numpy(), eps)[2:]]
-                for j, (_, flow, _, a1, a2, keep) in enumerate(occl_terms):
-                    occl[i, j] = metrics.flow_occlusion_mask_host(flow.numpy(), a1, a2, keep)[1]
-                if have_loss:
-                    losses[i] = float(loss)
+            for k, (_, device, host, _) in enumerate(report):
+                if on_gpu:
+                    device(buf[i, starts[k]:starts[k + 1]], loss)
+                else:
+                    buf[i, starts[k]:starts[k + 1]] = host(loss)
         if on_gpu:
-            packed = torch.cat([scores.reshape(-1), losses, smooth.reshape(-1), photo.reshape(-1), census.reshape(-1), consist.reshape(-1),
-                                occl.reshape(-1)]).cpu()          # the one synchronisation
-            scores = packed[:scores.numel()].numpy().astype(np.float64).reshape(num_batches, len(pairs), n, 3)
-            losses = packed[scores.size:scores.size + num_batches].numpy().astype(np.float64)
-            at = scores.size + num_batches
-            smooth = packed[at:at + smooth.numel()].numpy().astype(np.float64).reshape(num_batches, len(smooth_terms))
-            photo = packed[at + smooth.size:at + smooth.size + photo.numel()].numpy().astype(np.float64).reshape(num_batches, len(ms_terms), 3)
-            at += smooth.size + photo.size
-            census = packed[at:at + census.numel()].numpy().astype(np.float64).reshape(num_batches, len(census_terms))
-            at += census.size
-            consist = packed[at:at + consist.numel()].numpy().astype(np.float64).reshape(num_batches, len(consist_terms), 2)
-            occl = packed[at + consist.size:].numpy().astype(np.float64).reshape(num_batches, len(occl_terms), 3)
+            buf = buf.cpu().numpy().astype(np.float64)          # the one synchronisation
         result = {}
-        if have_loss:
-            result['loss'] = float(losses.mean())
-        for j, (name, _, _, max_val) in enumerate(pairs):
-            s = scores[:, j].reshape(-1, 3)
-            result[name + '/l1'] = float(s[:, metrics.L1].mean())
-            result[name + '/psnr'] = float(metrics.psnr(s[:, metrics.MSE], max_val).mean())
-            result[name + '/ssim'] = float(s[:, metrics.SSIM].mean())
-        for j, term in enumerate(smooth_terms):
-            result[term[0] + '/smoothness'] = float(smooth[:, j].mean())
-        for j, term in enumerate(ms_terms):
-            for l in range(term[4]):
-                result['%s/photo_x%d' % (term[0], 2 << l)] = float(photo[:, j, l].mean())
-        for j, term in enumerate(census_terms):
-            result[term[0] + '/census'] = float(census[:, j].mean())
-        for j, term in enumerate(consist_terms):
-            result[term[0] + '/consistency'] = float(consist[:, j, 0].mean())
-            result[term[0] + '/consistency_valid'] = float(consist[:, j, 1].mean())
-        for j, term in enumerate(occl_terms):
-            for k, what in enumerate(('visible', 'occluded', 'outside')):
-                result['%s/%s' % (term[0], what)] = float(occl[:, j, k].mean())
+        for k, entry in enumerate(report):
+            result.update(entry[3](buf[:, starts[k]:starts[k + 1]]))
         result['images'] = num_batches * n
         return result
+
+    def _report(self, pairs, n):
+        """What _evaluate() reports, in the order of the result's keys: one entry (columns, device, host, result) per quantity.
+        `columns` float32 values per batch; device(out, loss) writes them into the dense device vector `out`, asynchronously;
+        host(loss) returns them on a CPU graph (the numpy forms); result(block) turns the float64 [num_batches, columns] block into
+        [(key, value)].  `loss` is what forward() returned for the batch."""
+        from . import metrics
+        ms_kind = {'l1': 1, 'l2': 2}
+
+        def means(*keys):               # one key per column: the mean over the batches
+            return lambda block: [(key, float(block[:, c].mean())) for c, key in enumerate(keys)]
+        def into(value):                # a 0-d or [columns] device tensor -> out
+            return lambda out, loss: out.copy_(value(loss).reshape(-1), non_blocking=True)
+        def pair(name, pred, target, max_val):
+            def result(block):          # per image, not per batch: PSNR is averaged over the images
+                s = block.reshape(-1, 3)
+                return [(name + '/l1', float(s[:, metrics.L1].mean())), (name + '/psnr', float(metrics.psnr(s[:, metrics.MSE], max_val).mean())),
+                        (name + '/ssim', float(s[:, metrics.SSIM].mean()))]
+            return (3 * n, lambda out, loss: metrics.image_metrics(pred, target, max_val, out=out.view(n, 3)),
+                    lambda loss: metrics.image_metrics_host(pred.numpy(), target.numpy(), max_val).reshape(-1), result)
+        def smoothness(name, flow, guide, alpha, eps):
+            return (1, into(lambda loss: metrics.flow_smoothness(flow, guide, alpha, eps)),
+                    lambda loss: float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None, alpha, eps)[0]),
+                    means(name + '/smoothness'))
+        def multiscale(name, flow, src, target, levels, kind):
+            return (levels, into(lambda loss: metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1]),
+                    lambda loss: metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None, ms_kind[kind])[2],
+                    means(*['%s/photo_x%d' % (name, 2 << l) for l in range(levels)]))
+        def census(name, pred, target, max_val, radius, eps):
+            return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps)),
+                    lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0]),
+                    means(name + '/census'))
+        def consistency(name, flow, eps):
+            return (2, lambda out, loss: metrics.flow_consistency(flow, eps, 1.0, stats=out),
+                    lambda loss: [float(v) for v in metrics.flow_consistency_host(flow.numpy(), eps)[2:]],
+                    means(name + '/consistency', name + '/consistency_valid'))
+        def occlusion(name, flow, _, a1, a2, keep):
+            return (3, lambda out, loss: metrics.flow_occlusion_mask(flow, a1, a2, keep, stats=out),
+                    lambda loss: metrics.flow_occlusion_mask_host(flow.numpy(), a1, a2, keep)[1],
+                    means(*['%s/%s' % (name, what) for what in ('visible', 'occluded', 'outside')]))
+        report = [(1, into(lambda loss: loss), float, means('loss'))] if self.graph.loss_expr is not None else []
+        report += [pair(*p) for p in pairs]
+        for make, attr in ((smoothness, 'smoothness_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
+                           (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms')):
+            report += [make(*term) for term in getattr(self, attr, [])]
+        return report
 
     # ---- data-parallel hook
     def enable_data_parallel(self, world_size, group=None, comm=None, mode=None):

@@ -7,8 +7,9 @@ conv / deconv / linear are fused into that kernel's epilogue.
 """
 import math
 
-from .graph import (current_graph, Tensor, Storage, ScalarExpr, LossTerm, LOSS_SSIM, LOSS_CENSUS, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST, LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode,
-                    CopyConcatNode, TileNode, ResampleNode, ResamplerNode, OcclusionMaskNode, truncated_normal_init, random_normal_init, zeros_init)
+from .graph import (current_graph, Tensor, Storage, ScalarExpr, PixelTerm, SsimTerm, CensusTerm, SmoothTerm, MultiscaleTerm, ConsistTerm,
+                    LOSS_L1, LOSS_L2, ConvNode, LinearNode, ActNode, ViewNode, CopyConcatNode, TileNode, ResampleNode, ResamplerNode,
+                    OcclusionMaskNode, truncated_normal_init, random_normal_init, zeros_init)
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
 
@@ -80,7 +81,28 @@ def _loss_term(input1, input2, kind, mask=None):
     b_scale = 1.0
     if isinstance(b, _Scaled):
         b, b_scale = b.x, b.c
-    return ScalarExpr([(1.0, LossTerm(a, b, kind, mask, b_scale))])
+    return ScalarExpr([(1.0, PixelTerm(a, b, kind, mask, b_scale))])
+
+
+def _image_pair(op, input1, input2):
+    """(differentiated, other) operand of the symmetric image loss `op`: plain tensors, exactly one of them differentiated."""
+    for v in (input1, input2):
+        if isinstance(v, (_Masked, _Scaled)):
+            raise NotImplementedError("%s of a masked or scaled operand" % op)
+    if input2.requires_grad and not input1.requires_grad:
+        return input2, input1
+    if input1.requires_grad and input2.requires_grad:
+        raise NotImplementedError("loss between two differentiated tensors")
+    return input1, input2
+
+
+def _check_flow(op, flow):
+    """The flow operand of the op `op`: a usable tensor [N,H,W,2], neither masked nor scaled."""
+    if isinstance(flow, (_Masked, _Scaled)):
+        raise NotImplementedError("%s of a masked or scaled operand" % op)
+    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
+        raise ValueError("%s: flow must be a tensor [N,H,W,2], got %s" % (op, getattr(flow, 'shape', flow)))
+    _check_usable(flow)
 
 
 def euclidean_loss(input1, input2):
@@ -103,22 +125,14 @@ def ssim_loss(input1, input2, max_val=1.0):
     """1 - reduce_mean(tf.image.ssim(a, b, max_val)) for images of one size: the mean over images, fully-inside 11x11 Gaussian
     windows and channels (mv3d_ssim_loss; metrics.py states the definition).  Operands [N,H,W,C] with H, W >= 11 and C <= 4;
     exactly one of them is differentiated.  Masked and scaled operands are not supported."""
-    for v in (input1, input2):
-        if isinstance(v, (_Masked, _Scaled)):
-            raise NotImplementedError("ssim_loss of a masked or scaled operand")
-    a, b = input1, input2
-    # the differentiated operand goes first; SSIM is symmetric in its arguments
-    if b.requires_grad and not a.requires_grad:
-        a, b = b, a
-    elif a.requires_grad and b.requires_grad:
-        raise NotImplementedError("loss between two differentiated tensors")
+    a, b = _image_pair('ssim_loss', input1, input2)
     if len(a.shape) != 4 or tuple(a.shape) != tuple(b.shape):
         raise ValueError("ssim_loss: operands must be [N,H,W,C] of one shape, got %s and %s" % (a.shape, b.shape))
     if a.shape[1] < 11 or a.shape[2] < 11 or a.C > 4:
         raise ValueError("ssim_loss: needs H, W >= 11 and C <= 4, got %s" % (a.shape,))
     if not (math.isfinite(float(max_val)) and float(max_val) > 0):
         raise ValueError("ssim_loss: max_val must be finite and positive")
-    return ScalarExpr([(1.0, LossTerm(a, b, LOSS_SSIM, max_val=max_val))])
+    return ScalarExpr([(1.0, SsimTerm(a, b, max_val))])
 
 
 def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01):
@@ -129,17 +143,10 @@ def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01):
     value does not depend on the order, the gradient is the differentiated operand's).  Masked and scaled operands are not
     supported."""
     from .metrics import _census_scalars, _census_shape
-    for v in (input1, input2):
-        if isinstance(v, (_Masked, _Scaled)):
-            raise NotImplementedError("census_loss of a masked or scaled operand")
-    a, b = input1, input2
-    if b.requires_grad and not a.requires_grad:
-        a, b = b, a
-    elif a.requires_grad and b.requires_grad:
-        raise NotImplementedError("loss between two differentiated tensors")
+    a, b = _image_pair('census_loss', input1, input2)
     max_val, _, radius, eps = _census_scalars(max_val, 1.0, radius, eps)
     _census_shape(a.shape, b.shape, radius)
-    return ScalarExpr([(1.0, LossTerm(a, b, LOSS_CENSUS, max_val=max_val, eps=eps, radius=radius))])
+    return ScalarExpr([(1.0, CensusTerm(a, b, max_val, radius, eps))])
 
 
 def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
@@ -148,12 +155,9 @@ def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
     each difference weighted by exp(-edge_alpha * mean_k |difference of the guide|) when a guide image [N,H,W,1..4] is given.
     The flow must be differentiated (it is usually an intermediate tensor: its gradient from the consumer and this term's are
     added); the guide must not be.  Masked and scaled operands are not supported."""
-    for v in (flow, guide):
-        if isinstance(v, (_Masked, _Scaled)):
-            raise NotImplementedError("flow_smoothness_loss of a masked or scaled operand")
-    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
-        raise ValueError("flow_smoothness_loss: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
-    _check_usable(flow)
+    if isinstance(guide, (_Masked, _Scaled)):
+        raise NotImplementedError("flow_smoothness_loss of a masked or scaled operand")
+    _check_flow('flow_smoothness_loss', flow)
     if flow.shape[1] < 2 or flow.shape[2] < 2:
         raise ValueError("flow_smoothness_loss: needs H, W >= 2, got %s" % (flow.shape,))
     if not flow.requires_grad:
@@ -169,7 +173,7 @@ def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
         raise ValueError("flow_smoothness_loss: edge_alpha must be finite and >= 0")
     if not (math.isfinite(eps) and eps > 0):
         raise ValueError("flow_smoothness_loss: eps must be finite and positive")
-    return ScalarExpr([(1.0, LossTerm(flow, guide, LOSS_SMOOTH, edge_alpha=edge_alpha, eps=eps))])
+    return ScalarExpr([(1.0, SmoothTerm(flow, guide, edge_alpha, eps))])
 
 
 def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=None, kind='l2'):
@@ -195,8 +199,7 @@ def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=N
         raise ValueError("multiscale_photometric_loss: the flow is not differentiated (nothing to learn)")
     if src_img.requires_grad or target.requires_grad:
         raise NotImplementedError("multiscale_photometric_loss: the images are not differentiated; they must not require a gradient")
-    return ScalarExpr([(1.0, LossTerm(flow, target, LOSS_MULTISCALE, src=src_img, levels=levels, level_weights=weights,
-                                      pixel_kind=LOSS_L2 if kind == 'l2' else LOSS_L1))])
+    return ScalarExpr([(1.0, MultiscaleTerm(flow, target, src_img, levels, weights, LOSS_L2 if kind == 'l2' else LOSS_L1))])
 
 
 def flow_consistency_loss(flow, eps=1e-3):
@@ -207,16 +210,12 @@ def flow_consistency_loss(flow, eps=1e-3):
     The flow must be differentiated (it is usually an intermediate tensor: its gradient from the consumer and this term's are
     added).  Masked and scaled operands are not supported."""
     from .metrics import _consist_scalars, _consist_shape
-    if isinstance(flow, (_Masked, _Scaled)):
-        raise NotImplementedError("flow_consistency_loss of a masked or scaled operand")
-    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
-        raise ValueError("flow_consistency_loss: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
-    _check_usable(flow)
+    _check_flow('flow_consistency_loss', flow)
     _consist_shape(flow.shape)
     if not flow.requires_grad:
         raise ValueError("flow_consistency_loss: the flow is not differentiated (nothing to regularise)")
     eps, _ = _consist_scalars(float(eps), 1.0)
-    return ScalarExpr([(1.0, LossTerm(flow, None, LOSS_CONSIST, eps=eps))])
+    return ScalarExpr([(1.0, ConsistTerm(flow, eps))])
 
 
 def occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True):
@@ -227,11 +226,7 @@ def occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True):
     (requires_grad is False): use it as masked_euclidean_loss(gen, target, mask) or multiply(x, mask).  B must be even and the
     field square."""
     from .metrics import _consist_shape, _occlusion_scalars
-    if isinstance(flow, (_Masked, _Scaled)):
-        raise NotImplementedError("occlusion_mask of a masked or scaled operand")
-    if not isinstance(flow, Tensor) or len(flow.shape) != 4 or flow.shape[3] != 2:
-        raise ValueError("occlusion_mask: flow must be a tensor [N,H,W,2], got %s" % (getattr(flow, 'shape', flow),))
-    _check_usable(flow)
+    _check_flow('occlusion_mask', flow)
     _consist_shape(flow.shape)
     alpha1, alpha2, outside_visible = _occlusion_scalars(alpha1, alpha2, outside_visible)
     g = current_graph()

@@ -336,9 +336,9 @@ def test_a_term_without_a_place_in_the_reverse_pass_is_an_error(lib):
     g = m.graph
     term = [t for _, t in g.loss_expr.terms if t.a is m.flow_field][0]
     pending = [(0.25, term)]
-    g._smooth_all_placed([])
+    g._flow_terms_all_placed([])
     with pytest.raises(RuntimeError, match='no place'):
-        g._smooth_all_placed(pending)
+        g._flow_terms_all_placed(pending)
 
 
 def test_tinghui_and_the_angle_variants_take_the_switch(lib):
