@@ -73,6 +73,8 @@ STATUS_FUNCS = {
     "mv3d_image_metrics": [_i, _i, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp],
     "mv3d_ssim_loss": [_i, _i, _i, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_census_loss": [_i, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
+    "mv3d_ssim_loss_masked": [_i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
+    "mv3d_census_loss_masked": [_i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_smoothness": [_i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_consistency": [_i, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_occlusion_mask": [_i, _i, _i, _vp, _i, _f, _f, _i, _vp, _i, _vp, _vp, _sz, _vp],
@@ -146,6 +148,7 @@ OTHER_FUNCS = {
     "mv3d_image_metrics_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_ssim_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_census_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mv3d_ssim_loss_masked_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_flow_consistency_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_flow_occlusion_mask_workspace_bytes": (_sz, [_i, _i, _i]),

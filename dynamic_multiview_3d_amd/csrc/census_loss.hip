@@ -38,6 +38,13 @@
 // of one row of offsets are already a few hundred instructions.  A thread's 32 lanes of one tile row read consecutive floats,
 // so any pitch is free of bank conflicts in the passes over the tile; the pitches are odd for the ring, whose lanes run down
 // columns.  LDS at r = 3: 2 * 44 * 45 * 4 + 38 * 39 * 4 = 21.8 KB static.
+//
+// The masked form (mv3d_census_loss_masked, MASKED = true) weighs every valid pixel by a mask m [N,H,W,1] that is not
+// differentiated: census_loss_masked = (1 / (N Hv Wv)) sum m(p) rho(p), the count unchanged.  Pass 1 reads m(p) from global memory
+// once per tile or ring pixel, and only at valid pixels: the product m(p) * rho(p) is formed in fp32 and added into the double sum,
+// and the stored rho'(p) becomes (0.5 / root) * m(p), one fp32 multiply.  Everything behind it is the unmasked code, so a masked
+// pixel still receives a gradient as the neighbour of a visible one, m == 1 gives the unmasked bits and m == 0 gives zeros.  No
+// LDS is added.
 #include "image_common.h"
 
 namespace mv3d {
@@ -50,9 +57,9 @@ constexpr int CL_ROWS = CL_TILE * CL_TILE / CL_THREADS;    // tile pixels per th
 static_assert(CL_TILE == 32 && CL_THREADS == 256, "the thread mapping below: 32 lanes per tile row, 8 rows per round");
 
 struct ClArgs {
-    const float* a; const float* b;
+    const float* a; const float* b; const float* mask;      // mask: the masked form only
     double* part; float* loss; float* grad;
-    int N, H, W, C, a_ld, b_ld, grad_ld, tx, ty, accumulate, overwrite;
+    int N, H, W, C, a_ld, b_ld, mask_ld, grad_ld, tx, ty, accumulate, overwrite;
     float gs, inv_k, eps, eps2, gscale, weight;
     double count;
 };
@@ -95,7 +102,7 @@ __device__ __forceinline__ float census_root(float acc, const ClArgs& p, float* 
     return 0.5f / root;
 }
 
-template <int R>
+template <int R, bool MASKED>
 __global__ __launch_bounds__(CL_THREADS) void census_loss_tile_kernel(const ClArgs p) {
     using G = ClGeom<R>;
     __shared__ float s_ga[G::HALO * G::GP];
@@ -143,6 +150,11 @@ __global__ __launch_bounds__(CL_THREADS) void census_loss_tile_kernel(const ClAr
             const int at = (ly + 2 * R) * G::GP + px + 2 * R;
             float rho;
             dr = census_root(census_sum<R>(s_ga + at, s_gb + at), p, &rho);
+            if (MASKED) {
+                const float m = p.mask[(img + (int64_t)y * p.W + x) * p.mask_ld];
+                rho = m * rho;
+                dr = dr * m;
+            }
             sum[0] += (double)rho;
         }
         if (want_grad) s_dr[(ly + R) * G::DP + px + R] = dr;
@@ -169,6 +181,7 @@ __global__ __launch_bounds__(CL_THREADS) void census_loss_tile_kernel(const ClAr
                 const int at = (ry + R) * G::GP + rx + R;
                 float rho;
                 dr = census_root(census_sum<R>(s_ga + at, s_gb + at), p, &rho);
+                if (MASKED) dr = dr * p.mask[(img + (int64_t)y * p.W + x) * p.mask_ld];
             }
             s_dr[ry * G::DP + rx] = dr;
         }
@@ -219,10 +232,70 @@ __global__ __launch_bounds__(CL_THREADS) void census_loss_final_kernel(const ClA
     });
 }
 
-template <int R>
+template <int R, bool MASKED>
 int launch_tile(const ClArgs& p, int grid, hipStream_t s) {
-    census_loss_tile_kernel<R><<<grid, CL_THREADS, 0, s>>>(p);
+    census_loss_tile_kernel<R, MASKED><<<grid, CL_THREADS, 0, s>>>(p);
     return launched("census_loss_tile_kernel");
+}
+
+// Both entries: `mask` is null for mv3d_census_loss (fn names the entry in the messages).
+template <bool MASKED>
+int census_loss_entry(const char* fn, int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask,
+                      int mask_ld, int radius, float max_val, float eps, float weight, void* loss_accum, void* grad, int grad_ld,
+                      int grad_accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    int64_t total;
+    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
+    if (radius < 1 || radius > 3) return fail(MV3D_E_INVAL, "%s: radius (%d) outside 1..3", fn, radius);
+    if (int rc = check_patch_image_pair(fn, N, H, W, C, a_ld, b_ld, 2 * radius + 1, &total)) return rc;
+    if (MASKED && mask_ld < 1) return fail(MV3D_E_INVAL, "%s: mask_ld (%d) smaller than 1", fn, mask_ld);
+    if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
+    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
+    if (int rc = check_finite(fn, "max_val", max_val, true)) return rc;
+    if (int rc = check_finite(fn, "eps", eps, true)) return rc;
+    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
+    if (int rc = check_not_null(fn, {{"a", a}, {"b", b}, {"loss_accum", loss_accum}})) return rc;
+    if (MASKED)
+        if (int rc = check_not_null(fn, {{"mask", mask}})) return rc;
+    if (int rc = check_buffers(fn, MASKED ? "a, b, mask, loss_accum or grad" : "a, b, loss_accum or grad",
+                               (uintptr_t)a | (uintptr_t)b | (uintptr_t)mask | (uintptr_t)loss_accum | (uintptr_t)grad,
+                               workspace, workspace_bytes, tile_workspace_bytes(total, 1))) return rc;
+
+    const int K = (2 * radius + 1) * (2 * radius + 1) - 1;
+    ClArgs p = {};
+    p.a = (const float*)a; p.b = (const float*)b; p.mask = (const float*)mask; p.part = (double*)workspace;
+    p.loss = (float*)loss_accum; p.grad = (float*)grad;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.a_ld = a_ld; p.b_ld = b_ld; p.mask_ld = mask_ld; p.grad_ld = grad_ld;
+    p.tx = cdiv(W, CL_TILE); p.ty = cdiv(H, CL_TILE);
+    p.accumulate = grad_accumulate;
+    p.overwrite = take_loss_overwrite() ? 1 : 0;          // mv3d_loss_overwrite_next(): consumed by this call, kept by a recorded one
+    p.weight = weight;
+    p.count = (double)N * (double)(H - 2 * radius) * (double)(W - 2 * radius);
+    // the constants of the numpy twin, each formed in double and rounded to fp32 once
+    p.gs = (float)(255.0 / ((double)max_val * C));
+    p.inv_k = (float)(1.0 / K);
+    p.eps = eps;
+    p.eps2 = eps * eps;
+    p.gscale = (float)((double)weight * 255.0 / ((double)max_val * C) / ((double)K * p.count));
+
+    const double pixels = (double)N * H * W, elems = pixels * C;
+    // algorithmic bytes: both images once (and the mask's 4 B per pixel), the gradient written once (and read once when it
+    // accumulates), the tile sums written and read once.  FLOPs per pixel and offset: ~14 for the value (2 roots and 3 divisions
+    // counted as one each), ~22 more for the gradient, whose pass also repeats the value's on the ring.
+    const double grad_bytes = grad ? (grad_accumulate ? 8.0 : 4.0) : 0.0;
+    const double flops = pixels * K * (grad ? 14.0 * 1.4 + 22.0 : 14.0) + elems * 2.0;
+    const OpInfo tile_info{intern_label(MASKED ? "census_loss_masked_tile" : "census_loss_tile"), flops,
+                           elems * (8.0 + grad_bytes) + (MASKED ? pixels * 4.0 : 0.0) + (double)total * 8.0};
+    const int grid = (int)total;
+    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
+        return radius == 1 ? launch_tile<1, MASKED>(p, grid, s) : radius == 2 ? launch_tile<2, MASKED>(p, grid, s)
+                                                                              : launch_tile<3, MASKED>(p, grid, s);
+    });
+    if (rc) return rc;
+    const OpInfo final_info{intern_label(MASKED ? "census_loss_masked_final" : "census_loss_final"), 0.0, (double)total * 8.0 + 8.0};
+    return dispatch(stream, final_info, [=](hipStream_t s) {
+        census_loss_final_kernel<<<1, CL_THREADS, 0, s>>>(p);
+        return launched("census_loss_final_kernel");
+    });
 }
 
 }  // namespace
@@ -240,53 +313,15 @@ size_t mv3d_census_loss_workspace_bytes(int N, int H, int W, int C, int radius) 
 int mv3d_census_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, int radius, float max_val,
                      float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace,
                      size_t workspace_bytes, void* stream) {
-    const char* fn = "mv3d_census_loss";
-    int64_t total;
-    if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
-    if (radius < 1 || radius > 3) return fail(MV3D_E_INVAL, "%s: radius (%d) outside 1..3", fn, radius);
-    if (int rc = check_patch_image_pair(fn, N, H, W, C, a_ld, b_ld, 2 * radius + 1, &total)) return rc;
-    if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
-    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
-    if (int rc = check_finite(fn, "max_val", max_val, true)) return rc;
-    if (int rc = check_finite(fn, "eps", eps, true)) return rc;
-    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
-    if (int rc = check_not_null(fn, {{"a", a}, {"b", b}, {"loss_accum", loss_accum}})) return rc;
-    if (int rc = check_buffers(fn, "a, b, loss_accum or grad", (uintptr_t)a | (uintptr_t)b | (uintptr_t)loss_accum | (uintptr_t)grad,
-                               workspace, workspace_bytes, tile_workspace_bytes(total, 1))) return rc;
+    return census_loss_entry<false>("mv3d_census_loss", N, H, W, C, a, a_ld, b, b_ld, nullptr, 1, radius, max_val, eps, weight, loss_accum,
+                                    grad, grad_ld, grad_accumulate, workspace, workspace_bytes, stream);
+}
 
-    const int K = (2 * radius + 1) * (2 * radius + 1) - 1;
-    ClArgs p = {};
-    p.a = (const float*)a; p.b = (const float*)b; p.part = (double*)workspace; p.loss = (float*)loss_accum; p.grad = (float*)grad;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.a_ld = a_ld; p.b_ld = b_ld; p.grad_ld = grad_ld;
-    p.tx = cdiv(W, CL_TILE); p.ty = cdiv(H, CL_TILE);
-    p.accumulate = grad_accumulate;
-    p.overwrite = take_loss_overwrite() ? 1 : 0;          // mv3d_loss_overwrite_next(): consumed by this call, kept by a recorded one
-    p.weight = weight;
-    p.count = (double)N * (double)(H - 2 * radius) * (double)(W - 2 * radius);
-    // the constants of the numpy twin, each formed in double and rounded to fp32 once
-    p.gs = (float)(255.0 / ((double)max_val * C));
-    p.inv_k = (float)(1.0 / K);
-    p.eps = eps;
-    p.eps2 = eps * eps;
-    p.gscale = (float)((double)weight * 255.0 / ((double)max_val * C) / ((double)K * p.count));
-
-    const double pixels = (double)N * H * W, elems = pixels * C;
-    // algorithmic bytes: both images once, the gradient written once (and read once when it accumulates), the tile sums written
-    // and read once.  FLOPs per pixel and offset: ~14 for the value (2 roots and 3 divisions counted as one each), ~22 more for
-    // the gradient, whose pass also repeats the value's on the ring.
-    const double grad_bytes = grad ? (grad_accumulate ? 8.0 : 4.0) : 0.0;
-    const double flops = pixels * K * (grad ? 14.0 * 1.4 + 22.0 : 14.0) + elems * 2.0;
-    const OpInfo tile_info{intern_label("census_loss_tile"), flops, elems * (8.0 + grad_bytes) + (double)total * 8.0};
-    const int grid = (int)total;
-    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
-        return radius == 1 ? launch_tile<1>(p, grid, s) : radius == 2 ? launch_tile<2>(p, grid, s) : launch_tile<3>(p, grid, s);
-    });
-    if (rc) return rc;
-    const OpInfo final_info{intern_label("census_loss_final"), 0.0, (double)total * 8.0 + 8.0};
-    return dispatch(stream, final_info, [=](hipStream_t s) {
-        census_loss_final_kernel<<<1, CL_THREADS, 0, s>>>(p);
-        return launched("census_loss_final_kernel");
-    });
+int mv3d_census_loss_masked(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask, int mask_ld,
+                            int radius, float max_val, float eps, float weight, void* loss_accum, void* grad, int grad_ld,
+                            int grad_accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    return census_loss_entry<true>("mv3d_census_loss_masked", N, H, W, C, a, a_ld, b, b_ld, mask, mask_ld, radius, max_val, eps, weight,
+                                   loss_accum, grad, grad_ld, grad_accumulate, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

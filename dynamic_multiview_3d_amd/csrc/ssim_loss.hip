@@ -28,6 +28,13 @@
 //
 // LDS: staged rows are 53 floats apart, forward horizontal rows and coefficient rows 43, transposed horizontal rows 33: odd
 // pitches, because in the horizontal passes the lanes of a wave run down the rows.  2*52*53*4 + 4*52*43*4 = 57.8 KB static.
+//
+// The masked form (mv3d_ssim_loss_masked, MASKED = true) weighs every window by the mask m [N,H,W,1] at its centre, m_w =
+// m(oy + 5, ox + 5) for the window with origin (oy, ox); the mask is not differentiated.  Two double sums per tile, M = sum of m_w
+// and Sm = sum of fp32(m_w * S) over the channels and the tile's own windows, and loss = weight * (M / count - Sm / count) with the
+// count unchanged.  Dm, Ds, Dq of a window are each multiplied by m_w (one fp32 multiply each) before the transposed passes.
+// m_w is read from global memory in the vertical pass's thread mapping, where the lanes run along a window row: once per window, in
+// front of the channel loop, and kept in 7 registers over the channels.  No LDS is added.  m == 1 gives the unmasked bits (M == count exactly) and m == 0 gives zeros.
 #include "image_common.h"
 
 namespace mv3d {
@@ -51,17 +58,19 @@ static_assert(3 * SL_WIN * SL_TPITCH <= 2 * SL_HALO * SL_APITCH, "the transposed
 static_assert(3 * SL_WIN * SL_HPITCH <= 4 * SL_HALO * SL_HPITCH, "the coefficient maps fit over the horizontal results");
 
 struct SlArgs {
-    const float* a; const float* b;
+    const float* a; const float* b; const float* mask;      // mask: the masked form only
     double* part; float* loss; float* grad;
-    int N, H, W, C, a_ld, b_ld, grad_ld, tx, ty, accumulate, overwrite;
+    int N, H, W, C, a_ld, b_ld, mask_ld, grad_ld, tx, ty, accumulate, overwrite;
     float c1, c2, gscale, weight;
     float w[SL_TAPS];
 };
 
+template <bool MASKED>
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs p) {
+    constexpr int SUMS = MASKED ? 2 : 1;                   // the sum of S; masked: M, then Sm
     __shared__ float s_ab[2 * SL_HALO * SL_APITCH];        // a, b staged; later the transposed horizontal results
     __shared__ float s_h[4 * SL_HALO * SL_HPITCH];         // forward horizontal results; later Dm, Ds, Dq
-    __shared__ double s_red[SL_THREADS / 64];
+    __shared__ double s_red[SUMS * (SL_THREADS / 64)];
     float* const s_a = s_ab;
     float* const s_b = s_ab + SL_HALO * SL_APITCH;
     const int tiles = p.tx * p.ty;
@@ -72,7 +81,18 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
     const int64_t img = (int64_t)n * p.H * p.W;
     const int px = tid & 31, py = (tid >> 5) * 4;          // this thread's 4 pixels: rows py .. py+3 of column px
     const int wx = tid % SL_WIN, wy = (tid / SL_WIN) * SL_VR;      // its 7 windows: rows wy .. wy+6 of column wx (tid < 252)
-    double ssim[1] = {0.0};
+    double ssim[SUMS] = {};
+    float mw[SL_VR];                                       // masked: the mask at the centres of this thread's 7 windows
+    if (MASKED && tid < SL_WIN * (SL_WIN / SL_VR)) {
+        const int ox = x0 - SL_PAD + wx;
+#pragma unroll
+        for (int o = 0; o < SL_VR; ++o) {
+            const int oy = y0 - SL_PAD + wy + o;
+            mw[o] = 0.f;
+            if (oy >= 0 && oy < Hv && ox >= 0 && ox < Wv)
+                mw[o] = p.mask[(img + (int64_t)(oy + SL_TAPS / 2) * p.W + ox + SL_TAPS / 2) * p.mask_ld];
+        }
+    }
 
     for (int c = 0; c < p.C; ++c) {
         for (int i = tid; i < SL_HALO * SL_HALO; i += SL_THREADS) {
@@ -128,7 +148,19 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
                     dm[o] = ((my * (t.A2 - t.A1) - (mx * S) * (t.B2 - t.B1)) * 2.0f) / (t.B1 * t.B2);
                     ds[o] = (lum / t.B2) * 2.0f;
                     dq[o] = -(S / t.B2);
-                    if (oy >= y0 && ox >= x0) ssim[0] += (double)S;        // origin in the tile's own 32x32: counted here and only here
+                    if (MASKED) {
+                        dm[o] = dm[o] * mw[o];
+                        ds[o] = ds[o] * mw[o];
+                        dq[o] = dq[o] * mw[o];
+                    }
+                    if (oy >= y0 && ox >= x0) {                            // origin in the tile's own 32x32: counted here and only here
+                        if (MASKED) {
+                            ssim[0] += (double)mw[o];
+                            ssim[SUMS - 1] += (double)(mw[o] * S);
+                        } else {
+                            ssim[0] += (double)S;
+                        }
+                    }
                 }
             }
         }
@@ -181,7 +213,17 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_tile_kernel(const SlArgs
     }
 
     block_sum(ssim, s_red, tid);
-    if (tid == 0) p.part[blockIdx.x] = block_total(s_red, 0);
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < SUMS; ++q) p.part[(int64_t)blockIdx.x * SUMS + q] = block_total(s_red, q);
+    }
+}
+
+__global__ __launch_bounds__(SL_THREADS) void ssim_loss_masked_final_kernel(const SlArgs p) {
+    tile_sums_final<2>(p.part, (int64_t)p.N * p.tx * p.ty, p.loss, p.overwrite, [&](const double (&sum)[2]) {
+        const double windows = (double)p.N * (double)(p.H - SL_PAD) * (double)(p.W - SL_PAD) * (double)p.C;
+        return (float)((double)p.weight * (sum[0] / windows - sum[1] / windows));
+    });
 }
 
 __global__ __launch_bounds__(SL_THREADS) void ssim_loss_final_kernel(const SlArgs p) {
@@ -190,6 +232,60 @@ __global__ __launch_bounds__(SL_THREADS) void ssim_loss_final_kernel(const SlArg
         return (float)((double)p.weight * (1.0 - sum[0] / windows));
     });
 }
+
+// Both entries: `mask` is null for mv3d_ssim_loss (fn names the entry in the messages).
+template <bool MASKED>
+int ssim_loss_entry(const char* fn, int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask,
+                    int mask_ld, float max_val, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    constexpr int SUMS = MASKED ? 2 : 1;
+    int64_t total;
+    if (int rc = check_image_pair(fn, N, H, W, C, a_ld, b_ld, &total)) return rc;
+    if (MASKED && mask_ld < 1) return fail(MV3D_E_INVAL, "%s: mask_ld (%d) smaller than 1", fn, mask_ld);
+    if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
+    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
+    if (int rc = check_finite(fn, "max_val", max_val, true)) return rc;
+    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
+    if (int rc = check_not_null(fn, {{"a", a}, {"b", b}, {"loss_accum", loss_accum}})) return rc;
+    if (MASKED)
+        if (int rc = check_not_null(fn, {{"mask", mask}})) return rc;
+    if (int rc = check_buffers(fn, MASKED ? "a, b, mask, loss_accum or grad" : "a, b, loss_accum or grad",
+                               (uintptr_t)a | (uintptr_t)b | (uintptr_t)mask | (uintptr_t)loss_accum | (uintptr_t)grad,
+                               workspace, workspace_bytes, tile_workspace_bytes(total, SUMS))) return rc;
+
+    SlArgs p = {};
+    p.a = (const float*)a; p.b = (const float*)b; p.mask = (const float*)mask; p.part = (double*)workspace; p.loss = (float*)loss_accum; p.grad = (float*)grad;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.a_ld = a_ld; p.b_ld = b_ld; p.mask_ld = mask_ld; p.grad_ld = grad_ld;
+    p.tx = cdiv(W, SL_TILE); p.ty = cdiv(H, SL_TILE);
+    p.accumulate = grad_accumulate;
+    p.overwrite = take_loss_overwrite() ? 1 : 0;          // mv3d_loss_overwrite_next(): consumed by this call, kept by a recorded one
+    p.weight = weight;
+    const double windows = (double)N * (double)(H - SL_PAD) * (double)(W - SL_PAD) * (double)C;
+    p.gscale = (float)(-(double)weight / windows);
+    ssim_constants(max_val, &p.c1, &p.c2, p.w);
+
+    const double elems = (double)N * H * W * C;
+    // algorithmic bytes: both images once (and the mask's 4 B per pixel), the gradient written once (and read once when it accumulates), the tile sums written
+    // and read once.  FLOPs per element: 4 quantities x 2 passes x 11 taps x 2 forward, 3 x 2 x 11 x 2 transposed, ~40 for the
+    // window expression and the combination.
+    const double grad_bytes = grad ? (grad_accumulate ? 8.0 : 4.0) : 0.0;
+    const double flops = elems * (4.0 * 2 * SL_TAPS * 2 + (grad ? 3.0 * 2 * SL_TAPS * 2 + 40.0 : 12.0));
+    const OpInfo tile_info{intern_label(MASKED ? "ssim_loss_masked_tile" : "ssim_loss_tile"), flops,
+                           elems * (8.0 + grad_bytes) + (MASKED ? (double)N * H * W * 4.0 : 0.0) + (double)total * 8.0 * SUMS};
+    const int grid = (int)total;
+    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
+        ssim_loss_tile_kernel<MASKED><<<grid, SL_THREADS, 0, s>>>(p);
+        return launched("ssim_loss_tile_kernel");
+    });
+    if (rc) return rc;
+    const OpInfo final_info{intern_label(MASKED ? "ssim_loss_masked_final" : "ssim_loss_final"), 0.0, (double)total * 8.0 * SUMS + 8.0};
+    return dispatch(stream, final_info, [=](hipStream_t s) {
+        if (MASKED) ssim_loss_masked_final_kernel<<<1, SL_THREADS, 0, s>>>(p);
+        else ssim_loss_final_kernel<<<1, SL_THREADS, 0, s>>>(p);
+        return launched("ssim_loss_final_kernel");
+    });
+}
+
 
 }  // namespace
 }  // namespace mv3d
@@ -202,49 +298,22 @@ size_t mv3d_ssim_loss_workspace_bytes(int N, int H, int W, int C) {
     return tile_workspace_bytes(ssim_tile_count(N, H, W, C), 1);
 }
 
+size_t mv3d_ssim_loss_masked_workspace_bytes(int N, int H, int W, int C) {
+    return tile_workspace_bytes(ssim_tile_count(N, H, W, C), 2);
+}
+
 int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, float max_val, float weight,
                    void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
                    void* stream) {
-    const char* fn = "mv3d_ssim_loss";
-    int64_t total;
-    if (int rc = check_image_pair(fn, N, H, W, C, a_ld, b_ld, &total)) return rc;
-    if (grad && grad_ld < C) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than C (%d)", fn, grad_ld, C);
-    if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
-    if (int rc = check_finite(fn, "max_val", max_val, true)) return rc;
-    if (int rc = check_finite(fn, "weight", weight, false)) return rc;
-    if (int rc = check_not_null(fn, {{"a", a}, {"b", b}, {"loss_accum", loss_accum}})) return rc;
-    if (int rc = check_buffers(fn, "a, b, loss_accum or grad", (uintptr_t)a | (uintptr_t)b | (uintptr_t)loss_accum | (uintptr_t)grad,
-                               workspace, workspace_bytes, tile_workspace_bytes(total, 1))) return rc;
+    return ssim_loss_entry<false>("mv3d_ssim_loss", N, H, W, C, a, a_ld, b, b_ld, nullptr, 1, max_val, weight, loss_accum, grad, grad_ld,
+                                  grad_accumulate, workspace, workspace_bytes, stream);
+}
 
-    SlArgs p = {};
-    p.a = (const float*)a; p.b = (const float*)b; p.part = (double*)workspace; p.loss = (float*)loss_accum; p.grad = (float*)grad;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.a_ld = a_ld; p.b_ld = b_ld; p.grad_ld = grad_ld;
-    p.tx = cdiv(W, SL_TILE); p.ty = cdiv(H, SL_TILE);
-    p.accumulate = grad_accumulate;
-    p.overwrite = take_loss_overwrite() ? 1 : 0;          // mv3d_loss_overwrite_next(): consumed by this call, kept by a recorded one
-    p.weight = weight;
-    const double windows = (double)N * (double)(H - SL_PAD) * (double)(W - SL_PAD) * (double)C;
-    p.gscale = (float)(-(double)weight / windows);
-    ssim_constants(max_val, &p.c1, &p.c2, p.w);
-
-    const double elems = (double)N * H * W * C;
-    // algorithmic bytes: both images once, the gradient written once (and read once when it accumulates), the tile sums written
-    // and read once.  FLOPs per element: 4 quantities x 2 passes x 11 taps x 2 forward, 3 x 2 x 11 x 2 transposed, ~40 for the
-    // window expression and the combination.
-    const double grad_bytes = grad ? (grad_accumulate ? 8.0 : 4.0) : 0.0;
-    const double flops = elems * (4.0 * 2 * SL_TAPS * 2 + (grad ? 3.0 * 2 * SL_TAPS * 2 + 40.0 : 12.0));
-    const OpInfo tile_info{intern_label("ssim_loss_tile"), flops, elems * (8.0 + grad_bytes) + (double)total * 8.0};
-    const int grid = (int)total;
-    int rc = dispatch(stream, tile_info, [=](hipStream_t s) {
-        ssim_loss_tile_kernel<<<grid, SL_THREADS, 0, s>>>(p);
-        return launched("ssim_loss_tile_kernel");
-    });
-    if (rc) return rc;
-    const OpInfo final_info{intern_label("ssim_loss_final"), 0.0, (double)total * 8.0 + 8.0};
-    return dispatch(stream, final_info, [=](hipStream_t s) {
-        ssim_loss_final_kernel<<<1, SL_THREADS, 0, s>>>(p);
-        return launched("ssim_loss_final_kernel");
-    });
+int mv3d_ssim_loss_masked(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask, int mask_ld,
+                          float max_val, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return ssim_loss_entry<true>("mv3d_ssim_loss_masked", N, H, W, C, a, a_ld, b, b_ld, mask, mask_ld, max_val, weight, loss_accum, grad,
+                                 grad_ld, grad_accumulate, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -343,30 +343,37 @@ class PixelTerm(LossTerm):
 
 
 class SsimTerm(LossTerm):
-    """1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss).  The workspace holds the per-tile sums (not the shared scratch: the
-    term's two launches must find it untouched whatever runs beside them)."""
+    """1 - mean SSIM at dynamic range max_val (mv3d_ssim_loss), or with a one-channel mask its masked form
+    (mv3d_ssim_loss_masked).  The workspace holds the per-tile sums (not the shared scratch: the term's two launches must find it
+    untouched whatever runs beside them)."""
     kind, order = LOSS_SSIM, 1
 
-    def __init__(self, a, b, max_val=1.0):
-        LossTerm.__init__(self, a, b)
+    def __init__(self, a, b, max_val=1.0, mask=None):
+        LossTerm.__init__(self, a, b, mask)
         self.max_val = float(max_val)
 
     def workspace_bytes(self, lib):
-        return self._nonzero(lib.ssim_loss_workspace_bytes(*self.a.shape),
+        size = lib.ssim_loss_workspace_bytes if self.mask is None else lib.ssim_loss_masked_workspace_bytes
+        return self._nonzero(size(*self.a.shape),
                              "ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (self.a.shape,))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b = self.a, self.b
+        a, b, m = self.a, self.b, self.mask
+        if m is not None:
+            g.lib.ssim_loss_masked(*a.shape, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld, self.max_val, float(w), g.loss_buf.data_ptr(),
+                                   a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+            return
         g.lib.ssim_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.max_val, float(w), g.loss_buf.data_ptr(),
                         a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
 
 
 class CensusTerm(LossTerm):
-    """The soft census loss over (2 radius + 1)^2 patches at dynamic range max_val with Charbonnier eps (mv3d_census_loss)."""
+    """The soft census loss over (2 radius + 1)^2 patches at dynamic range max_val with Charbonnier eps (mv3d_census_loss), or with
+    a one-channel mask its masked form (mv3d_census_loss_masked; the same workspace)."""
     kind, order = LOSS_CENSUS, 2
 
-    def __init__(self, a, b, max_val=1.0, radius=3, eps=1e-3):
-        LossTerm.__init__(self, a, b)
+    def __init__(self, a, b, max_val=1.0, radius=3, eps=1e-3, mask=None):
+        LossTerm.__init__(self, a, b, mask)
         self.max_val, self.radius, self.eps = float(max_val), int(radius), float(eps)
 
     def workspace_bytes(self, lib):
@@ -374,7 +381,12 @@ class CensusTerm(LossTerm):
                              "census_loss: operands of shape %s at radius %d are outside what mv3d_census_loss takes" % (self.a.shape, self.radius))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b = self.a, self.b
+        a, b, m = self.a, self.b, self.mask
+        if m is not None:
+            g.lib.census_loss_masked(*a.shape, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld, self.radius, self.max_val, self.eps, float(w),
+                                     g.loss_buf.data_ptr(), a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0,
+                                     self.ws.data_ptr(), self.ws.numel(), g.stream)
+            return
         g.lib.census_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.radius, self.max_val, self.eps, float(w), g.loss_buf.data_ptr(),
                           a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
 
@@ -1054,6 +1066,8 @@ class Graph:
             w, t = uses[0]
             if not isinstance(t, PixelTerm):
                 continue            # the SSIM and census losses need gen and write their gradient in HBM: they never fuse
+            # (A masked SSIM or census term beside the masked pixel loss is a second use of gen: the head stays unfused, so the
+            # mask node's own occl_mask launch sits in the forward plan in front of every loss launch that reads the mask.)
             if t.a is not gen or t.b_scale != 1.0 or t.b.requires_grad or t.b.rows != gen.rows or t.b.C != gen.C:
                 continue
             occl = None

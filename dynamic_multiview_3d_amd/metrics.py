@@ -95,13 +95,35 @@ def _transposed_filter(d, w):
     return _valid_filter(p, w)
 
 
-def ssim_loss_host(pred, target, max_val=1.0, dtype=np.float64, weight=1.0):
+def _host_mask(op, mask, shape, dtype):
+    """The mask of a masked image loss as [N,H,W] in `dtype`: [N,H,W,1] (or [N,H,W]) over the operands' N, H, W, finite."""
+    m = np.asarray(mask)
+    if m.ndim == 4 and m.shape[3] == 1:
+        m = m[..., 0]
+    if m.shape != tuple(shape[:3]):
+        raise ValueError("%s: mask must be [N,H,W,1] over the operands' %s, got %s" % (op, tuple(shape[:3]), np.asarray(mask).shape))
+    m = m.astype(dtype)
+    if not np.all(np.isfinite(m)):
+        raise ValueError("%s: mask must be finite" % op)
+    return m
+
+
+def ssim_loss_host(pred, target, max_val=1.0, dtype=np.float64, weight=1.0, mask=None):
     """(loss, grad): loss = weight * (1 - mean of ssim_map over images, windows and channels), a scalar of `dtype`, and grad =
     d loss / d pred, [N,H,W,C] in `dtype`; every step in `dtype` arithmetic.  At float32 this states mv3d_ssim_loss's own
     operation order (csrc/ssim_loss.hip); only the sum behind the mean differs (the kernel keeps it in double).
 
     Per window:  Dm = dS/dmx = 2 (my (A2 - A1) - mx S (B2 - B1)) / (B1 B2),  Ds = dS/dsab = 2 lum / B2,  Dq = dS/ds2 = -S / B2
-    grad = -weight / count * (Ft(Dm) + target * Ft(Ds) + 2 pred * Ft(Dq));  pred == target gives exactly (0, zeros)."""
+    grad = -weight / count * (Ft(Dm) + target * Ft(Ds) + 2 pred * Ft(Dq));  pred == target gives exactly (0, zeros).
+
+    mask (None = the code above, untouched): m [N,H,W,1], any finite values, never differentiated, indexed by the pixel of pred
+    (mv3d_ssim_loss_masked).  A window with origin (oy, ox) takes the mask at its centre, m_w = m(oy + 5, ox + 5), the same for
+    every channel:
+      loss = weight * (mean(m_w broadcast over C) - mean(m_w * S)),   both means over the N Hv Wv C windows (a masked window still
+      counts: masked_euclidean_loss keeps its mean over all pixels the same way); the kernel keeps the two sums in double;
+      Dm, Ds, Dq are each multiplied by m_w (one multiply each) before the transposed passes.
+    m == 1 gives the unmasked numbers bit for bit, m == 0 gives (0, zeros), pred == target gives exactly 0 under any mask, and
+    both results are linear in m."""
     dtype = np.dtype(dtype).type
     a, b, max_val = _ssim_operands(pred, target, max_val, dtype)
     weight = float(np.float32(weight))                       # the C ABI takes a float
@@ -111,10 +133,16 @@ def ssim_loss_host(pred, target, max_val=1.0, dtype=np.float64, weight=1.0):
     two = dtype(2)
     mx, my, A1, B1, A2, B2, lum, S = _ssim_parts(a, b, max_val, dtype)
     count = S.size
-    loss = dtype(weight * float(dtype(1) - S.mean(dtype=dtype)))
     dm = ((my * (A2 - A1) - (mx * S) * (B2 - B1)) * two) / (B1 * B2)
     ds = (lum / B2) * two
     dq = -(S / B2)
+    if mask is None:
+        loss = dtype(weight * float(dtype(1) - S.mean(dtype=dtype)))
+    else:
+        half = WINDOW_TAPS // 2
+        mw = _host_mask('ssim_loss', mask, a.shape, dtype)[:, half:half + S.shape[1], half:half + S.shape[2], None]
+        loss = dtype(weight * float(np.broadcast_to(mw, S.shape).mean(dtype=dtype) - (mw * S).mean(dtype=dtype)))
+        dm, ds, dq = dm * mw, ds * mw, dq * mw
     g = (_transposed_filter(dm, w) + b * _transposed_filter(ds, w)) + (a * two) * _transposed_filter(dq, w)
     return loss, g * dtype(-weight / count)
 
@@ -166,6 +194,18 @@ def _operand(x, what):
     return x.ptr, tuple(x.shape), x.ld, x.graph.device
 
 
+def _mask_operand(op, mask, shape, dev):
+    """(data pointer, pixel stride) of the mask of a masked image loss: a graph Tensor or a torch device tensor [N,H,W,1] over the
+    operands' N, H, W on their device (a channel of a wider tensor works)."""
+    import torch
+    pm, shape_m, m_ld, dev_m = _operand(mask, 'mask')
+    if shape_m != tuple(shape[:3]) + (1,):
+        raise ValueError("%s: mask must be [N,H,W,1] over the operands' %s, got %s" % (op, tuple(shape[:3]), shape_m))
+    if not _same_device(dev_m, dev):
+        raise ValueError("%s: mask on %s, operands on %s" % (op, dev_m, dev))
+    return pm, m_ld
+
+
 _workspaces = {}        # torch device -> uint8 workspace tensor, grown on demand (calls on one stream share it in order)
 
 
@@ -206,9 +246,10 @@ def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
     return out
 
 
-def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False, stream=None):
+def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False, stream=None, mask=None):
     """mv3d_ssim_loss on device memory: weight * (1 - mean SSIM) of pred against target, and optionally its gradient with
-    respect to pred.  pred / target: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with
+    respect to pred.  mask (None = mv3d_ssim_loss, exactly as before): a float32 [N,H,W,1] graph Tensor or torch device tensor
+    (a channel of a wider tensor works); the call is then mv3d_ssim_loss_masked (ssim_loss_host states the definition).  pred / target: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with
     the operand rules of image_metrics.  grad: an optional float32 device tensor of pred's shape with one pixel stride (a
     channel slice of a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream`
     (default: torch's current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
@@ -231,10 +272,17 @@ def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False
             raise ValueError("ssim_loss: grad %s on %s does not match pred %s on %s" % (shape_g, dev_g, shape, dev))
     out = torch.zeros((), dtype=torch.float32, device=dev)
     lib = _lib.lib()
-    nbytes = int(lib.ssim_loss_workspace_bytes(n, h, w, c))
-    ws = _workspace(dev, nbytes)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if mask is not None:
+        pm, m_ld = _mask_operand('ssim_loss', mask, shape, dev)
+        nbytes = int(lib.ssim_loss_masked_workspace_bytes(n, h, w, c))
+        ws = _workspace(dev, nbytes)
+        lib.ssim_loss_masked(n, h, w, c, pa, a_ld, pb, b_ld, pm, m_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld,
+                             1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+        return out
+    nbytes = int(lib.ssim_loss_workspace_bytes(n, h, w, c))
+    ws = _workspace(dev, nbytes)
     lib.ssim_loss(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld, 1 if accumulate else 0,
                   ws.data_ptr(), nbytes, stream)
     return out
@@ -797,7 +845,7 @@ def census_offsets(radius):
     return [(dy, dx) for dy in range(-radius, radius + 1) for dx in range(-radius, radius + 1) if (dy, dx) != (0, 0)]
 
 
-def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, eps=0.01):
+def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, eps=0.01, mask=None):
     """(loss, grad) of the soft census (ternary) loss of Meister et al. ("UnFlow") / Liu et al. ("DDFlow"): loss = weight *
     census_loss, a scalar of `dtype`, and grad = d loss / d a, [N,H,W,C] in `dtype`; every step in `dtype` arithmetic.  At float32
     this states mv3d_census_loss's own operation order (csrc/census_loss.hip); only the sum behind the mean differs (the kernel
@@ -825,7 +873,16 @@ def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, 
     terms in offset order and multiplies by 1/K rounded once; phi = (0.162 u) / ((0.1 + e)^2 (R_a R_a R_a)); the second sum of
     the bracket runs in offset order and the first in reverse offset order (the order in which a kernel that gathers at q meets
     them: phi(q-o, o) == -phi(q, -o) exactly); the bracket is first - rho'(q) * second, times weight 255 / (max_val C K N Hv Wv)
-    rounded once."""
+    rounded once.
+
+    mask (None = the code above, untouched): m [N,H,W,1], any finite values, never differentiated, indexed by the pixel of a and
+    read only at valid pixels (mv3d_census_loss_masked):
+      census_loss_masked = (1 / (N Hv Wv)) sum over n and the valid p of m(p) rho(p)     the count stays N Hv Wv, as
+                                                                                         masked_euclidean_loss keeps its mean
+    The product m(p) * rho(p) is formed first, then summed (the kernel adds it into its double sum).  In the gradient rho'(p)
+    becomes (0.5 / root(p)) * m(p), one multiply; everything behind it is unchanged, so a masked pixel still receives a gradient
+    as the neighbour of a visible one.  m == 1 gives the unmasked numbers bit for bit, m == 0 gives (0, zeros), a == b gives
+    exactly 0 under any mask, and both results are linear in m."""
     dtype = np.dtype(dtype).type
     max_val, weight, r, eps = _census_scalars(max_val, weight, radius, eps)
     a, b = np.asarray(a).astype(dtype), np.asarray(b).astype(dtype)
@@ -861,8 +918,12 @@ def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, 
     eps_t = dtype(eps)
     root = np.sqrt(dist + eps_t * eps_t)
     rho = dist / (root + eps_t)
-    loss = dtype(weight * (float(rho.sum(dtype=dtype)) / count))
     dr = half / root
+    if mask is not None:
+        mv = _host_mask('census_loss', mask, a.shape, dtype)[:, r:r + hv, r:r + wv]
+        rho = mv * rho
+        dr = dr * mv
+    loss = dtype(weight * (float(rho.sum(dtype=dtype)) / count))
     second = np.zeros((n, hv, wv), dtype)
     for f in phi:
         second = second + f
@@ -874,9 +935,11 @@ def census_loss_host(a, b, max_val=1.0, dtype=np.float32, weight=1.0, radius=3, 
     return loss, np.ascontiguousarray(np.broadcast_to(grad[..., None], a.shape))
 
 
-def census_loss(a, b, max_val=1.0, weight=1.0, radius=3, eps=0.01, grad=None, accumulate=False, stream=None):
+def census_loss(a, b, max_val=1.0, weight=1.0, radius=3, eps=0.01, grad=None, accumulate=False, stream=None, mask=None):
     """mv3d_census_loss on device memory: weight * census_loss of a (the prediction) against b (the target), and optionally its
-    gradient with respect to a.  a / b: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with the
+    gradient with respect to a.  mask (None = mv3d_census_loss, exactly as before): a float32 [N,H,W,1] graph Tensor or torch
+    device tensor (a channel of a wider tensor works); the call is then mv3d_census_loss_masked (census_loss_host states the
+    definition).  a / b: graph Tensors (channel views included) or torch device tensors, [N,H,W,C] float32, with the
     operand rules of image_metrics.  grad: an optional float32 device tensor of a's shape with one pixel stride (a channel slice of
     a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's
     current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
@@ -903,6 +966,11 @@ def census_loss(a, b, max_val=1.0, weight=1.0, radius=3, eps=0.01, grad=None, ac
     ws = _workspace(dev, nbytes)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if mask is not None:
+        pm, m_ld = _mask_operand('census_loss', mask, shape, dev)
+        lib.census_loss_masked(n, h, w, c, pa, a_ld, pb, b_ld, pm, m_ld, int(radius), float(max_val), float(eps), float(weight),
+                               out.data_ptr(), pg, g_ld, 1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+        return out
     lib.census_loss(n, h, w, c, pa, a_ld, pb, b_ld, int(radius), float(max_val), float(eps), float(weight), out.data_ptr(), pg, g_ld,
                     1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
     return out

@@ -236,9 +236,10 @@ def occlusion_from_conf(conf):
     which leaves the loss and the recorded plans as they are), conf['occlusion_alpha1'] (default 0.01), conf['occlusion_alpha2']
     (default 0.5, in pixels squared) and conf['occlusion_outside'] ('keep', the default: a pixel whose flow leaves the image keeps
     its loss, or 'mask': it loses it, UnFlow's choice).  The switch needs conf['pair_swap'] (pair_swap.py): the mask comes from the
-    forward-backward residual of sample n against sample n + batch_size / 2.  The SSIM, census and multi-scale terms have no
-    masked form: combined with conf['ssim_loss_weight'], conf['census_loss_weight'] or conf['multiscale_loss_levels'] the switch
-    is refused.  Raises ValueError on a non-bool switch, a bool, negative or non-finite alpha1, an alpha2 <= 0, an unknown
+    forward-backward residual of sample n against sample n + batch_size / 2.  Combined with conf['ssim_loss_weight'] or
+    conf['census_loss_weight'] the switch is refused unless conf['occlusion_mask_image_terms'] opts into their masked forms
+    (occlusion_image_terms_from_conf); the multi-scale term has no masked form, so conf['multiscale_loss_levels'] is refused
+    either way.  Raises ValueError on a non-bool switch, a bool, negative or non-finite alpha1, an alpha2 <= 0, an unknown
     conf['occlusion_outside'], a missing conf['pair_swap'] or one of those combinations, before any device work."""
     from .pair_swap import pair_swap_from_conf
     on = conf.get('occlusion_mask')
@@ -266,13 +267,39 @@ def occlusion_from_conf(conf):
     if not pair_swap_from_conf(conf):
         raise ValueError("conf['occlusion_mask'] needs conf['pair_swap'] = True: the mask pairs sample n of a batch with sample "
                          "n + batch_size / 2, which the pair-swapped feed makes the reversed pair")
-    if ssim_weight_from_conf(conf) > 0:
-        raise ValueError("conf['occlusion_mask'] does not combine with conf['ssim_loss_weight']: the SSIM loss has no masked form")
-    if census_from_conf(conf)[0] > 0:
-        raise ValueError("conf['occlusion_mask'] does not combine with conf['census_loss_weight']: the census loss has no masked form")
+    image_terms = _occlusion_image_terms_switch(conf)
+    if ssim_weight_from_conf(conf) > 0 and not image_terms:
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['ssim_loss_weight']: the SSIM loss has no masked form "
+                         "unless conf['occlusion_mask_image_terms'] = True asks for it")
+    if census_from_conf(conf)[0] > 0 and not image_terms:
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['census_loss_weight']: the census loss has no masked form "
+                         "unless conf['occlusion_mask_image_terms'] = True asks for it")
     if multiscale_loss_from_conf(conf)[0] > 0:
         raise ValueError("conf['occlusion_mask'] does not combine with conf['multiscale_loss_levels']: the multi-scale loss has no masked form")
     return alphas[0], alphas[1], outside == 'keep'
+
+
+def _occlusion_image_terms_switch(conf):
+    """conf['occlusion_mask_image_terms'] as a bool (absent, None or False = off); ValueError on anything that is not a bool."""
+    on = conf.get('occlusion_mask_image_terms')
+    if on is not None and not isinstance(on, (bool, np.bool_)):
+        raise ValueError("conf['occlusion_mask_image_terms'] must be True or False (or None for off), got %r" % (on,))
+    return bool(on)
+
+
+def occlusion_image_terms_from_conf(conf):
+    """True when the SSIM and census terms take the head's occlusion mask: conf['occlusion_mask_image_terms'] (absent, None or
+    False = off, which leaves every conf behaving, raising and recording as it did without the key).  True needs
+    conf['occlusion_mask']: ssim_term() and census_term() then pass the mask head_loss() created (UnFlow's data term is the census
+    loss under the forward-backward mask; DDFlow and ARFlow mask census and SSIM the same way), and conf['occlusion_mask']
+    combines with conf['ssim_loss_weight'] and conf['census_loss_weight'].  With neither weight set the key changes nothing.
+    Raises ValueError on a value that is not a bool (with the switch off as well) and on True without conf['occlusion_mask'], before
+    any device work."""
+    on = _occlusion_image_terms_switch(conf)
+    if on and occlusion_from_conf(conf) is None:
+        raise ValueError("conf['occlusion_mask_image_terms'] needs conf['occlusion_mask'] = True: the masked SSIM and census "
+                         "terms take the occlusion_mask of the head loss")
+    return on
 
 
 def multiscale_loss_from_conf(conf):
@@ -332,6 +359,8 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['flow_consistency_weight']" % type(self).__name__)
         if occlusion_from_conf(self.conf) is not None and not self.supports_occlusion_mask:
             raise ValueError("%s does not support conf['occlusion_mask']" % type(self).__name__)
+        if occlusion_image_terms_from_conf(self.conf) and not self.supports_occlusion_mask:
+            raise ValueError("%s does not support conf['occlusion_mask_image_terms']" % type(self).__name__)
 
     def _note_term(self, attr, entry):
         """One more entry of a per-term list that evaluate() reports from (_report); the list exists only once a term was added."""
@@ -349,7 +378,19 @@ class ModelBase(object):
             return euclidean_loss(gen, target)
         mask = occlusion_mask(flow, *occl)
         self._note_term('occlusion_terms', (name, flow, mask) + tuple(occl))      # (name, flow, mask tensor, alpha1, alpha2, outside_visible)
+        self._note_term('_head_masks', (gen, mask))
         return masked_euclidean_loss(gen, target, mask)
+
+    def _image_term_mask(self, op, pred):
+        """The mask ssim_term() / census_term() pass on: None unless conf['occlusion_mask_image_terms'] is on, then the occlusion
+        mask head_loss() created for this prediction."""
+        if not occlusion_image_terms_from_conf(self.conf):
+            return None
+        for gen, mask in getattr(self, '_head_masks', []):
+            if gen is pred:
+                return mask
+        raise RuntimeError("%s: conf['occlusion_mask_image_terms'] is on, but head_loss() made no occlusion mask for this prediction "
+                           "(call head_loss() first)" % op)
 
     def occlusion_mask(self, name='flow'):
         """The occlusion mask [B,H,W,1] of the last step (forward, train or evaluate) as a device tensor: a view of the graph's
@@ -418,25 +459,37 @@ class ModelBase(object):
 
     def ssim_term(self, pred, target):
         """conf['ssim_loss_weight'] * ssim_loss(pred, target, max_val) with max_val from this model's eval_pairs() entry of the
-        pair, or 0 when the switch is absent or 0 (the graph then records exactly what it recorded without the key)."""
+        pair, or 0 when the switch is absent or 0 (the graph then records exactly what it recorded without the key).  With
+        conf['occlusion_mask_image_terms'] the term takes the head's occlusion mask (ssim_loss(..., mask=)), and evaluate() reports
+        the unweighted masked term as '<pair>/ssim_loss_masked' ('<pair>/ssim' stays the unmasked figure)."""
         from .tf_utils import ssim_loss
         w = ssim_weight_from_conf(self.conf)
         if w == 0:
             return 0
-        return ssim_loss(pred, target, self._eval_pair('ssim_term', pred, target)[1]) * w
+        name, max_val = self._eval_pair('ssim_term', pred, target)
+        mask = self._image_term_mask('ssim_term', pred)
+        term = ssim_loss(pred, target, max_val, mask=mask) * w
+        if mask is not None:
+            self._note_term('masked_image_terms', (name, 'ssim_loss_masked', pred, target, mask, max_val, None, None))
+        return term
 
     def census_term(self, pred, target):
         """conf['census_loss_weight'] * census_loss(pred, target, max_val, radius, eps) with max_val from this model's eval_pairs()
         entry of the pair and radius, eps from conf['census_loss_radius' / '_eps'], or 0 when the switch is absent or 0 (the graph
         then records exactly what it recorded without the key).  Raises ValueError for an image smaller than the patch.
-        evaluate() reports the unweighted term as '<pair>/census'."""
+        evaluate() reports the unweighted term as '<pair>/census'.  With conf['occlusion_mask_image_terms'] the term takes the head's
+        occlusion mask (census_loss(..., mask=)); '<pair>/census' stays the unmasked figure, comparable across runs, and
+        '<pair>/census_masked' is the unweighted term as trained."""
         from .tf_utils import census_loss
         w, radius, eps = census_from_conf(self.conf)
         if w == 0:
             return 0
         name, max_val = self._eval_pair('census_term', pred, target)
-        term = census_loss(pred, target, max_val, radius, eps) * w
+        mask = self._image_term_mask('census_term', pred)
+        term = census_loss(pred, target, max_val, radius, eps, mask=mask) * w
         self._note_term('census_terms', (name, pred, target, max_val, radius, eps))        # name: the pair's
+        if mask is not None:
+            self._note_term('masked_image_terms', (name, 'census_masked', pred, target, mask, max_val, radius, eps))
         return term
 
     def _make_graph(self, device, seed):
@@ -603,10 +656,19 @@ class ModelBase(object):
             return (3, lambda out, loss: metrics.flow_occlusion_mask(flow, a1, a2, keep, stats=out),
                     lambda loss: metrics.flow_occlusion_mask_host(flow.numpy(), a1, a2, keep)[1],
                     means(*['%s/%s' % (name, what) for what in ('visible', 'occluded', 'outside')]))
+        def masked_image(name, what, pred, target, mask, max_val, radius, eps):       # the masked SSIM / census term as trained
+            if what == 'census_masked':
+                return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps, mask=mask)),
+                        lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps,
+                                                                    mask=mask.numpy())[0]),
+                        means(name + '/census_masked'))
+            return (1, into(lambda loss: metrics.ssim_loss(pred, target, max_val, 1.0, mask=mask)),
+                    lambda loss: float(metrics.ssim_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, mask=mask.numpy())[0]),
+                    means(name + '/ssim_loss_masked'))
         report = [(1, into(lambda loss: loss), float, means('loss'))] if self.graph.loss_expr is not None else []
         report += [pair(*p) for p in pairs]
         for make, attr in ((smoothness, 'smoothness_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
-                           (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms')):
+                           (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms'), (masked_image, 'masked_image_terms')):
             report += [make(*term) for term in getattr(self, attr, [])]
         return report
 

@@ -96,6 +96,21 @@ def _image_pair(op, input1, input2):
     return input1, input2
 
 
+def _image_mask(op, mask, a):
+    """The mask operand of the image loss `op` on the differentiated operand a, or None: a graph tensor [N,H,W,1] over a's N, H, W
+    that is not differentiated (an occlusion_mask() output, or a one-channel view of a constant tensor)."""
+    if mask is None:
+        return None
+    if isinstance(mask, (_Masked, _Scaled)):
+        raise NotImplementedError("%s of a masked or scaled operand" % op)
+    if not isinstance(mask, Tensor) or len(mask.shape) != 4 or tuple(mask.shape) != tuple(a.shape[:3]) + (1,):
+        raise ValueError("%s: mask must be a tensor [N,H,W,1] over the operands' %s, got %s" % (op, tuple(a.shape[:3]), getattr(mask, 'shape', mask)))
+    if mask.requires_grad:
+        raise ValueError("%s: the mask is not differentiated; it must not require a gradient" % op)
+    _check_usable(mask)
+    return mask
+
+
 def _check_flow(op, flow):
     """The flow operand of the op `op`: a usable tensor [N,H,W,2], neither masked nor scaled."""
     if isinstance(flow, (_Masked, _Scaled)):
@@ -121,10 +136,12 @@ def masked_euclidean_loss(input1, input2, mask):
     return _loss_term(input1, input2, 2, mask)
 
 
-def ssim_loss(input1, input2, max_val=1.0):
+def ssim_loss(input1, input2, max_val=1.0, mask=None):
     """1 - reduce_mean(tf.image.ssim(a, b, max_val)) for images of one size: the mean over images, fully-inside 11x11 Gaussian
     windows and channels (mv3d_ssim_loss; metrics.py states the definition).  Operands [N,H,W,C] with H, W >= 11 and C <= 4;
-    exactly one of them is differentiated.  Masked and scaled operands are not supported."""
+    exactly one of them is differentiated.  Masked and scaled operands are not supported.  mask (optional): a graph tensor
+    [N,H,W,1] that is not differentiated, usually occlusion_mask(flow); every window is then weighed by the mask at its centre and
+    the mean keeps its count (mv3d_ssim_loss_masked; metrics.ssim_loss_host states the definition)."""
     a, b = _image_pair('ssim_loss', input1, input2)
     if len(a.shape) != 4 or tuple(a.shape) != tuple(b.shape):
         raise ValueError("ssim_loss: operands must be [N,H,W,C] of one shape, got %s and %s" % (a.shape, b.shape))
@@ -132,21 +149,23 @@ def ssim_loss(input1, input2, max_val=1.0):
         raise ValueError("ssim_loss: needs H, W >= 11 and C <= 4, got %s" % (a.shape,))
     if not (math.isfinite(float(max_val)) and float(max_val) > 0):
         raise ValueError("ssim_loss: max_val must be finite and positive")
-    return ScalarExpr([(1.0, SsimTerm(a, b, max_val))])
+    return ScalarExpr([(1.0, SsimTerm(a, b, max_val, _image_mask('ssim_loss', mask, a)))])
 
 
-def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01):
+def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01, mask=None):
     """The soft census (ternary) loss of the prediction against the target (mv3d_census_loss; metrics.census_loss_host states the
     definition): the mean over images and fully-inside (2 radius + 1)^2 patches of the Charbonnier penalty (parameter eps) of the
     distance between the two images' soft census signatures, computed on the channel mean scaled to 0..255 by max_val.  Operands
     [N,H,W,C] with H, W >= 2 radius + 1, C <= 4 and radius in 1..3; exactly one of them is differentiated, and it goes first (the
     value does not depend on the order, the gradient is the differentiated operand's).  Masked and scaled operands are not
-    supported."""
+    supported.  mask (optional): a graph tensor [N,H,W,1] that is not differentiated, usually occlusion_mask(flow); every valid
+    pixel's penalty is then weighed by the mask there and the mean keeps its count (mv3d_census_loss_masked;
+    metrics.census_loss_host states the definition)."""
     from .metrics import _census_scalars, _census_shape
     a, b = _image_pair('census_loss', input1, input2)
     max_val, _, radius, eps = _census_scalars(max_val, 1.0, radius, eps)
     _census_shape(a.shape, b.shape, radius)
-    return ScalarExpr([(1.0, CensusTerm(a, b, max_val, radius, eps))])
+    return ScalarExpr([(1.0, CensusTerm(a, b, max_val, radius, eps, _image_mask('census_loss', mask, a)))])
 
 
 def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):

@@ -346,6 +346,25 @@ int mv3d_ssim_loss(int N, int H, int W, int C, const void* a, int a_ld, const vo
                    void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* The occlusion-masked form of mv3d_ssim_loss: the same arguments plus mask [N,H,W,1] fp32 with pixel stride mask_ld >= 1 (a
+ * channel of a wider tensor works), indexed by the pixel of the prediction.  The mask is never differentiated and may hold any
+ * finite values (mv3d_flow_occlusion_mask produces 0 / 1).  A window with origin (oy, ox) takes the mask at its centre, m_w =
+ * m(oy + 5, ox + 5):
+ *   ssim_loss_masked = M / count - Sm / count,   M = sum over c, w of m_w,   Sm = sum over c, w of fp32(m_w * S),
+ *   count = N*Hv*Wv*C as in the unmasked entry (a masked window still counts: masked_euclidean_loss keeps its mean the same way);
+ *   Dm, Ds, Dq of a window are each multiplied by m_w (one fp32 multiply) before the transposed passes.
+ * M and Sm are double sums in the fixed order of the unmasked entry (plan labels ssim_loss_masked_tile, ssim_loss_masked_final; the
+ * workspace holds 2 doubles per tile: mv3d_ssim_loss_masked_workspace_bytes(), 0 for a shape the entry refuses).  m == 1
+ * everywhere gives the bits of mv3d_ssim_loss in the loss word and in every gradient element; m == 0 gives a term of +0 (for
+ * weight >= 0) and a gradient of zeros; a == b gives exactly 0 under any mask; the term is linear in m.  Everything else (the
+ * overwrite flag, grad_accumulate, determinism, value bits with and without grad) is as for mv3d_ssim_loss.
+ * Errors: those of mv3d_ssim_loss, and MV3D_E_INVAL for mask_ld < 1, a null mask or a mask that is not 4-byte aligned, all before
+ * any launch. */
+size_t mv3d_ssim_loss_masked_workspace_bytes(int N, int H, int W, int C);
+int mv3d_ssim_loss_masked(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask, int mask_ld,
+                          float max_val, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- census (ternary) loss: value and gradient with respect to the prediction --------------------------------------------
  * The soft census transform of Meister et al. ("UnFlow") / Liu et al. ("DDFlow").  a (prediction), b (target) [N,H,W,C] fp32 with
  * pixel strides a_ld / b_ld (channel-slice views work), C in 1..4; radius r in {1, 2, 3}; K = (2r+1)^2 - 1 offsets o of the
@@ -384,6 +403,23 @@ size_t mv3d_census_loss_workspace_bytes(int N, int H, int W, int C, int radius);
 int mv3d_census_loss(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, int radius, float max_val,
                      float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* The occlusion-masked form of mv3d_census_loss: the same arguments plus mask [N,H,W,1] fp32 with pixel stride mask_ld >= 1 (a
+ * channel of a wider tensor works), indexed by the pixel of the prediction.  The mask is never differentiated, may hold any finite
+ * values (mv3d_flow_occlusion_mask produces 0 / 1) and is read only at valid pixels.
+ *   census_loss_masked = (1 / (N Hv Wv)) sum over n and the valid p of m(p) rho(p)
+ * The count stays N Hv Wv (masked_euclidean_loss keeps its mean over all pixels the same way).  The product m(p) * rho(p) is formed
+ * in fp32 and added into the double sum.  In the gradient rho'(p) becomes (0.5 / root(p)) * m(p), one fp32 multiply; everything
+ * behind it is unchanged, so a masked pixel still receives a gradient as the neighbour of a visible one.  m == 1 everywhere gives
+ * the bits of mv3d_census_loss in the loss word and in every gradient element; m == 0 gives a term of +0 (for weight >= 0) and a
+ * gradient of zeros; a == b gives exactly 0 under any mask; the term is linear in m.  The workspace is that of
+ * mv3d_census_loss_workspace_bytes(); the plan labels are census_loss_masked_tile, census_loss_masked_final.  Everything else (the
+ * overwrite flag, grad_accumulate, determinism, value bits with and without grad) is as for mv3d_census_loss.
+ * Errors: those of mv3d_census_loss, and MV3D_E_INVAL for mask_ld < 1, a null mask or a mask that is not 4-byte aligned, all
+ * before any launch. */
+int mv3d_census_loss_masked(int N, int H, int W, int C, const void* a, int a_ld, const void* b, int b_ld, const void* mask, int mask_ld,
+                            int radius, float max_val, float eps, float weight, void* loss_accum, void* grad, int grad_ld,
+                            int grad_accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- edge-aware flow smoothness: value and gradient with respect to the flow --------------------------------------------
  * flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view works), H, W >= 2; guide (optional; NULL with

@@ -1,0 +1,218 @@
+"""mv3d_ssim_loss_masked on the GPU, through the C ABI, against metrics.ssim_loss_host(mask=) evaluated in float64 on the same fp32
+inputs, and against mv3d_ssim_loss itself.
+
+Tolerance (the rule of tests/test_gpu_census_loss.py, in tests/masked_image_cases.py allowed()): the kernel may differ from the
+float64 twin by at most 4 x the float32 twin's own float32-to-float64 gap on the same inputs, with floors of 2e-6 absolute for the
+loss and 2e-6 of the float64 gradient's L2 norm / largest magnitude; 4e-6 * weight absolute for a == b and where the float64
+gradient is exactly zero.  Wherever the float64 gradient is non-zero and a != b its relative L2 error may not exceed 1e-3;
+tests/test_masked_image_losses_host.py shows that the reference alone stays inside that cap.  Every figure is printed before it is
+asserted.
+
+Shapes (masked_image_cases.SSIM_CASES): one window; one window row with W crossing a tile edge; ragged edges; a tile with
+neighbours.  Masks: ones, zeros, zero blocks across the tile edges and the border, 30 % ones, uniform fractions, and the mask as
+channel 2 of a 4-channel tensor."""
+import numpy as np
+import pytest
+import torch
+
+from dynamic_multiview_3d_amd import _lib, metrics
+from tests import masked_image_cases as MC
+from tests.gpu_utils import DEV, stream
+from tests.test_masked_image_losses_host import SSIM_REFUSALS, ssim_call
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 7.25
+KIND = 'ssim'
+CASES = sorted(MC.SSIM_CASES)
+
+
+def _bits(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def _run(lib, ta, tb, tm, off, c, weight=1.0, loss=None, grad=None, accumulate=0, ws=None, m_off=0):
+    """One call on the channel view [off, off + c) of dense device tensors; tm None = the unmasked entry; the mask is channel m_off
+    of tm; grad (optional) has the operands' layout."""
+    n, h, w, ld = ta.shape
+    size = lib.ssim_loss_workspace_bytes if tm is None else lib.ssim_loss_masked_workspace_bytes
+    nb = int(size(n, h, w, c))
+    assert nb >= (8 if tm is None else 16) * n * -(-h // 32) * -(-w // 32)
+    if ws is None:
+        ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    if loss is None:
+        loss = torch.zeros(1, dtype=torch.float32, device=DEV)
+    pg = grad.data_ptr() + 4 * off if grad is not None else None
+    if tm is None:
+        lib.ssim_loss(n, h, w, c, ta.data_ptr() + 4 * off, ld, tb.data_ptr() + 4 * off, ld, MC.MAX_VAL, weight, loss.data_ptr(), pg, ld, accumulate,
+                      ws.data_ptr(), nb, stream())
+    else:
+        assert tuple(tm.shape[:3]) == (n, h, w) and tm.is_contiguous()
+        lib.ssim_loss_masked(n, h, w, c, ta.data_ptr() + 4 * off, ld, tb.data_ptr() + 4 * off, ld, tm.data_ptr() + 4 * m_off, tm.shape[3], MC.MAX_VAL,
+                             weight, loss.data_ptr(), pg, ld, accumulate, ws.data_ptr(), nb, stream())
+    return loss
+
+
+def _upload(case, family):
+    a, b = MC.inputs(KIND, case, family)
+    return torch.from_numpy(a.copy()).to(DEV), torch.from_numpy(b.copy()).to(DEV)
+
+
+@pytest.mark.parametrize("family", MC.FAMILIES)
+@pytest.mark.parametrize("case", CASES)
+def test_parity_with_the_numpy_definition(case, family):
+    lib = _lib.lib()
+    ta, tb = _upload(case, family)
+    n, h, w, c = ta.shape
+    same = family == 'same'
+    for mf in MC.MASKS:
+        tm = torch.from_numpy(MC.mask(KIND, case, mf).copy()).to(DEV)
+        grad = torch.full((n, h, w, c), SENTINEL, dtype=torch.float32, device=DEV)
+        loss = _run(lib, ta, tb, tm, 0, c, grad=grad)
+        loss_only = _run(lib, ta, tb, tm, 0, c)
+        torch.cuda.synchronize()
+        got_l, got32 = float(loss.cpu()[0]), grad.cpu().numpy()
+        label = '%s %s %s' % (case, family, mf)
+        assert not np.any(got32 == SENTINEL), label
+        assert np.all(np.isfinite(got32)) and np.isfinite(got_l)
+
+        l64, g64, l32, g32 = MC.reference(KIND, case, family, mf, 0, c)
+        la, a2, am = MC.allowed(l64, g64, l32, g32, same)
+        err = got32.astype(np.float64) - g64
+        e2, em, n2 = np.linalg.norm(err), np.abs(err).max(), np.linalg.norm(g64)
+        print('%-32s loss %.6f err %.2e allowed %.2e | grad L2 err %.2e allowed %.2e norm %.2e | max err %.2e allowed %.2e | differs from the float32 twin in %d of %d'
+              % (label, l64, abs(got_l - l64), la, e2, a2, n2, em, am, int(np.count_nonzero(got32 != g32)), got32.size))
+        assert abs(got_l - l64) <= la, (label, abs(got_l - l64), la)
+        assert e2 <= a2, (label, e2, a2)
+        assert em <= am, (label, em, am)
+        if same or mf == 'zeros':
+            assert _bits(loss)[0] == 0, label                               # a == b under any mask, or m == 0: a +0 loss word
+        if mf == 'zeros':
+            assert not np.any(got32), label                                 # ... and a gradient of zeros
+        elif not same and n2 > 0:
+            assert e2 <= 1e-3 * n2, (label, e2 / n2)
+        assert _bits(loss)[0] == _bits(loss_only)[0], label                # the value does not depend on whether a gradient was asked for
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_a_mask_of_ones_gives_the_bits_of_the_unmasked_entry_and_a_view_keeps_the_sentinel(case):
+    lib = _lib.lib()
+    for family in ('noise', 'random'):
+        ta, tb = _upload(case, family)
+        ld = ta.shape[3]
+        tm = torch.ones(tuple(ta.shape[:3]) + (1,), dtype=torch.float32, device=DEV)
+        for off, c in [(0, ld)] + ([(1, ld - 1)] if ld > 1 else []):
+            grads = [torch.full(tuple(ta.shape), SENTINEL, dtype=torch.float32, device=DEV) for _ in range(2)]
+            plain = _run(lib, ta, tb, None, off, c, 0.75, grad=grads[0])
+            ones = _run(lib, ta, tb, tm, off, c, 0.75, grad=grads[1])
+            torch.cuda.synchronize()
+            assert _bits(plain)[0] == _bits(ones)[0] and np.array_equal(_bits(grads[0]), _bits(grads[1])), (case, family, off)
+            got = grads[1].cpu().numpy()
+            assert np.all(got[..., :off] == SENTINEL) and not np.any(got[..., off:] == SENTINEL), (case, family, off)
+
+
+def test_the_mask_may_be_a_channel_of_a_wider_tensor():
+    lib = _lib.lib()
+    case = 'ragged'
+    ta, tb = _upload(case, 'random')
+    m = MC.mask(KIND, case, 'fraction')
+    wide = np.full(m.shape[:3] + (4,), np.nan, np.float32)                  # a read of any other channel poisons the result
+    wide[..., 2:3] = m
+    tm, tw = torch.from_numpy(m.copy()).to(DEV), torch.from_numpy(wide).to(DEV)
+    grads = [torch.full(tuple(ta.shape), SENTINEL, dtype=torch.float32, device=DEV) for _ in range(3)]
+    dense = _run(lib, ta, tb, tm, 0, 3, grad=grads[0])
+    strided = _run(lib, ta, tb, tw, 0, 3, grad=grads[1], m_off=2)
+    mirror = metrics.ssim_loss(ta, tb, MC.MAX_VAL, 1.0, grad=grads[2], mask=tw[..., 2:3])
+    torch.cuda.synchronize()
+    assert _bits(dense)[0] == _bits(strided)[0] == _bits(mirror.reshape(1))[0] and np.isfinite(float(dense))
+    assert np.array_equal(_bits(grads[0]), _bits(grads[1])) and np.array_equal(_bits(grads[0]), _bits(grads[2]))
+    with pytest.raises(ValueError, match='mask'):
+        metrics.ssim_loss(ta, tb, mask=tw)
+    with pytest.raises(ValueError, match='mask'):
+        metrics.ssim_loss(ta, tb, mask=tm[:, :-1])
+
+
+def test_grad_accumulate_adds_onto_what_is_there_bit_for_bit():
+    lib = _lib.lib()
+    for case, off, c in (('inner', 0, 2), ('ragged', 1, 2), ('row', 0, 3)):
+        ta, tb = _upload(case, 'noise')
+        tm = torch.from_numpy(MC.mask(KIND, case, 'fraction').copy()).to(DEV)
+        stored = torch.full(tuple(ta.shape), SENTINEL, dtype=torch.float32, device=DEV)
+        _run(lib, ta, tb, tm, off, c, 0.5, grad=stored)
+        base = torch.from_numpy(np.random.default_rng(4).normal(0, 1e-4, tuple(ta.shape)).astype(np.float32)).to(DEV)
+        accum = base.clone()
+        _run(lib, ta, tb, tm, off, c, 0.5, grad=accum, accumulate=1)
+        torch.cuda.synchronize()
+        want = base.cpu().numpy().copy()
+        want[..., off:off + c] = want[..., off:off + c] + stored.cpu().numpy()[..., off:off + c]       # one fp32 addition per element
+        assert np.array_equal(accum.cpu().numpy().view(np.uint32), want.view(np.uint32)), case
+
+
+def test_two_runs_and_a_replayed_plan_give_the_same_bits():
+    lib = _lib.lib()
+    ta, tb = _upload('ragged', 'noise')
+    n, h, w, c = ta.shape
+    tm = torch.from_numpy(MC.mask(KIND, 'ragged', 'blocks').copy()).to(DEV)
+    nb = int(lib.ssim_loss_masked_workspace_bytes(n, h, w, c))
+    ws = torch.zeros(nb, dtype=torch.uint8, device=DEV)
+    losses = [torch.full((1,), SENTINEL, dtype=torch.float32, device=DEV) for _ in range(3)]
+    grads = [torch.full((n, h, w, c), SENTINEL, dtype=torch.float32, device=DEV) for _ in range(3)]
+    for l, g in zip(losses[:2], grads[:2]):
+        lib.loss_overwrite_next()
+        _run(lib, ta, tb, tm, 0, c, loss=l, grad=g, ws=ws)
+        ws.zero_()                                                          # no state survives in the workspace between calls
+    plan = lib.plan_create()
+    lib.plan_begin(plan)
+    try:
+        lib.loss_overwrite_next()                                           # a recorded call keeps the flag it saw
+        lib.ssim_loss_masked(n, h, w, c, ta.data_ptr(), c, tb.data_ptr(), c, tm.data_ptr(), 1, MC.MAX_VAL, 1.0, losses[2].data_ptr(),
+                             grads[2].data_ptr(), c, 0, ws.data_ptr(), nb, None)
+    finally:
+        lib.plan_end()
+    ops = _lib.plan_ops(plan)
+    assert [o[0] for o in ops] == ['ssim_loss_masked_tile', 'ssim_loss_masked_final']
+    elems, tiles = n * h * w * c, n * 2 * 3
+    assert ops[0][2] == elems * 12.0 + n * h * w * 4.0 + tiles * 16.0 and ops[0][1] > 0     # the unmasked bytes, 4 B per pixel, 2 sums per tile
+    assert ops[1][2] == tiles * 16.0 + 8.0
+    torch.cuda.synchronize()
+    assert losses[2].cpu().numpy()[0] == SENTINEL and np.all(grads[2].cpu().numpy() == SENTINEL)      # recording launches nothing
+    for _ in range(2):                                                      # replayed twice: it stores both times
+        lib.plan_run(plan, stream())
+        ws.zero_()
+    torch.cuda.synchronize()
+    lib.plan_destroy(plan)
+    lb = [_bits(l)[0] for l in losses]
+    gb = [_bits(g) for g in grads]
+    assert lb[0] == lb[1] == lb[2]
+    assert np.array_equal(gb[0], gb[1]) and np.array_equal(gb[0], gb[2])
+    assert not np.any(grads[0].cpu().numpy() == SENTINEL)
+
+
+def test_argument_errors_leave_loss_and_grad_untouched():
+    lib = _lib.lib()
+    n, h, w, c = 2, 16, 20, 3
+    ta = torch.rand((n, h, w, c), device=DEV)
+    tb = torch.rand((n, h, w, c), device=DEV)
+    tm = torch.rand((n, h, w, 1), device=DEV)
+    loss = torch.full((1,), SENTINEL, dtype=torch.float32, device=DEV)
+    grad = torch.full((n, h, w, c), SENTINEL, dtype=torch.float32, device=DEV)
+    nb = int(lib.ssim_loss_masked_workspace_bytes(n, h, w, c))
+    ws = torch.empty(nb + 64, dtype=torch.uint8, device=DEV)
+    ok = dict(N=n, H=h, W=w, C=c, a=ta.data_ptr(), a_ld=c, b=tb.data_ptr(), b_ld=c, mask=tm.data_ptr(), mask_ld=1, max_val=1.0, weight=1.0,
+              loss=loss.data_ptr(), grad=grad.data_ptr(), grad_ld=c, acc=0, ws=ws.data_ptr(), ws_bytes=nb)
+    lib.loss_overwrite_next()                                  # stays pending through every refusal
+    for kw, code, word in SSIM_REFUSALS:
+        kw = dict(kw)
+        for key, t in (('a', ta), ('mask', tm), ('grad', grad), ('ws', ws)):       # the made-up misaligned addresses become real ones
+            if kw.get(key) is not None:
+                kw[key] = t.data_ptr() + (8 if key == 'ws' else 2)
+        if 'ws_bytes' in kw:
+            kw['ws_bytes'] = nb - 1
+        assert ssim_call(lib, stream(), ok, **kw) == code, kw
+        assert word in lib.last_error() and 'mv3d_ssim_loss_masked' in lib.last_error(), (kw, lib.last_error())
+    torch.cuda.synchronize()
+    assert loss.cpu().numpy()[0] == SENTINEL and np.all(grad.cpu().numpy() == SENTINEL)
+    assert ssim_call(lib, stream(), ok) == 0
+    torch.cuda.synchronize()
+    got = loss.cpu().numpy()[0]
+    assert 0 < got < 1.5 and not np.any(grad.cpu().numpy() == SENTINEL)          # stored over the sentinel: the flag was still pending
