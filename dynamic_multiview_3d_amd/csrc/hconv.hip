@@ -495,7 +495,9 @@ int try_hconv(const IgemmParams& p, void* ws, size_t ws_bytes, void* stream, con
     if (p.fold || (nph != 1 && nph != 4)) return 1;
     if (p.Ka % 16 != 0 || p.a_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(p.A) & 15)) return 1;
     const bool kmajor_in = kmajor_of(p);
-    const bool b3 = !(disabled_paths() & 4096);          // split-bf16 matrix-core path (bconv.hip); off = exact fp32 MFMA
+    // split-bf16 matrix-core path (bconv.hip); off = exact fp32 MFMA.  A tanh forward takes the exact kernels: tanh maps the
+    // split products' absolute error, which grows with the layer, onto an output of at most 1
+    const bool b3 = !(disabled_paths() & 4096) && p.act != MV3D_ACT_TANH;
     if (!b3 && !kmajor_in && ((p.w_ns % 4) != 0 || (reinterpret_cast<uintptr_t>(p.Wt) & 15))) return 1;
     const int Hp = p.Hp[0], Wp = p.Wp[0];
     if (nph == 4 && (p.Hp[1] != Hp || p.Wp[1] != Wp)) return 1;
