@@ -82,6 +82,8 @@ STATUS_FUNCS = {
                                           _vp, _vp, _vp, _sz, _vp],
     "mv3d_multiscale_warp_loss": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _i, _i, _i,
                                   _vp, _sz, _vp],
+    "mv3d_multiscale_warp_loss_masked": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _i,
+                                         _i, _i, _vp, _sz, _vp],
     "mv3d_pixel_loss": [_i64, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
     "mv3d_loss_overwrite_next": [],
     "mv3d_pixel_loss_strided": [_i64, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _f, _vp, _vp, _i, _vp],

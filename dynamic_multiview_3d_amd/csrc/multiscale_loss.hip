@@ -30,6 +30,15 @@
 //            two gradient channels: one writer per element, the flow read and grad touched once whatever L is.
 //   final    one workgroup adds the tiles' three sums in a fixed order, writes T_l and adds (or stores) the term.
 // H and W are multiples of 2^L and tile origins multiples of 32, so a coarse block lies wholly inside the image or wholly outside.
+//
+// The masked form (mv3d_multiscale_warp_loss_masked, MASKED = true) weighs every coarse pixel by a mask m [N,H,W,1] over the flow's
+// grid that is not differentiated: m_l = pool_l(m), the same pooling, so a coarse pixel counts by its visible share and a 0/1 mask
+// pools exactly.  T_l = (1 / (N H_l W_l)) sum m_l sum_c phi(d_c), the count unchanged; a coarse pixel's channel sum is formed in
+// double as before and the level sum adds (double)m_l * s; the scaled dgen becomes (d * s_l) * m_l (or (sign(d) * s_l) * m_l), the
+// mask multiplying last.  Everything behind it is the unmasked code: m == 1 gives the unmasked bits, m == 0 gives +0 and zeros.
+// The mask lies on the flow's grid, which the tile kernel already stages and halves: stage A loads the mask tile beside the flow
+// tile, stage B halves it beside the flow, stage C reads m_l from LDS (4096 + 1344 B more).  The pyramid launch and the workspace
+// know nothing of it; a call with pyramid_ready pools the mask again from its 4 B per pixel.
 #include "image_common.h"
 
 namespace mv3d {
@@ -42,10 +51,10 @@ constexpr int MS_L1 = 16, MS_L2 = 8, MS_L3 = 4;             // coarse pixels per
 constexpr int MS_OFF2 = MS_L1 * MS_L1, MS_OFF3 = MS_OFF2 + MS_L2 * MS_L2, MS_COARSE = MS_OFF3 + MS_L3 * MS_L3;      // 256, 320, 336
 
 struct MsArgs {
-    const float* src; const float* flow; const float* target;
+    const float* src; const float* flow; const float* target; const float* mask;    // mask: the masked form only
     float* psrc[MS_LEVELS]; float* ptgt[MS_LEVELS];         // the pyramids in the workspace, dense
     double* part; float* loss; float* level_values; float* grad;
-    int N, H, W, Hs, Ws, levels, kind, src_ld, flow_ld, target_ld, grad_ld, accumulate, overwrite, flow_vec, grad_vec;
+    int N, H, W, Hs, Ws, levels, kind, src_ld, flow_ld, target_ld, mask_ld, grad_ld, accumulate, overwrite, flow_vec, grad_vec;
     int tx, ty, sx, sy, src_tiles;                          // tiles of the flow / target, of src, N * sx * sy
     float gscale[MS_LEVELS];                                // s_l
     double weight[MS_LEVELS], count[MS_LEVELS];             // w_l, N H_l W_l
@@ -110,10 +119,12 @@ __device__ __forceinline__ void ms_tap(const float* img, int Ws, int Hs, int y, 
     for (int c = 0; c < C; ++c) { const float t = a[c]; v[c] = ok ? t : 0.f; }
 }
 
-template <int C>
+template <int C, bool MASKED>
 __global__ __launch_bounds__(MS_THREADS) void ms_loss_tile_kernel(const MsArgs p) {
     __shared__ float2 s_f0[MS_TILE * MS_TILE];              // the flow tile
     __shared__ float2 s_f[MS_COARSE];                       // its levels 1, 2, 3 at 0, 256, 320
+    __shared__ float s_m0[MASKED ? MS_TILE * MS_TILE : 1];  // the mask tile and its levels, laid out like s_f0 and s_f; the
+    __shared__ float s_m[MASKED ? MS_COARSE : 1];           // unmasked kernel never names them
     __shared__ float2 s_g[MS_COARSE];                       // the scaled warp gradients, same layout
     __shared__ double s_red[MS_LEVELS * (MS_THREADS / 64)];
     const int tiles = p.tx * p.ty;
@@ -134,6 +145,11 @@ __global__ __launch_bounds__(MS_THREADS) void ms_loss_tile_kernel(const MsArgs p
             else { f.x = a[0]; f.y = a[1]; }
         }
         s_f0[r * MS_TILE + lo] = f;
+        if constexpr (MASKED) {
+            float m = 0.f;
+            if (i < p.H && j < p.W) m = p.mask[(img + (int64_t)i * p.W + j) * p.mask_ld];
+            s_m0[r * MS_TILE + lo] = m;
+        }
     }
     __syncthreads();
     // ---- B: halved three times, one thread per coarse pixel
@@ -141,18 +157,30 @@ __global__ __launch_bounds__(MS_THREADS) void ms_loss_tile_kernel(const MsArgs p
         const int r = tid >> 4, q = tid & 15;
         const float2* a = s_f0 + (2 * r) * MS_TILE + 2 * q;
         s_f[tid] = pool4(a[0], a[1], a[MS_TILE], a[MS_TILE + 1]);
+        if constexpr (MASKED) {
+            const float* m = s_m0 + (2 * r) * MS_TILE + 2 * q;
+            s_m[tid] = pool4(m[0], m[1], m[MS_TILE], m[MS_TILE + 1]);
+        }
     }
     __syncthreads();
     if (tid < MS_L2 * MS_L2) {
         const int r = tid >> 3, q = tid & 7;
         const float2* a = s_f + (2 * r) * MS_L1 + 2 * q;
         s_f[MS_OFF2 + tid] = pool4(a[0], a[1], a[MS_L1], a[MS_L1 + 1]);
+        if constexpr (MASKED) {
+            const float* m = s_m + (2 * r) * MS_L1 + 2 * q;
+            s_m[MS_OFF2 + tid] = pool4(m[0], m[1], m[MS_L1], m[MS_L1 + 1]);
+        }
     }
     __syncthreads();
     if (tid < MS_L3 * MS_L3) {
         const int r = tid >> 2, q = tid & 3;
         const float2* a = s_f + MS_OFF2 + (2 * r) * MS_L2 + 2 * q;
         s_f[MS_OFF3 + tid] = pool4(a[0], a[1], a[MS_L2], a[MS_L2 + 1]);
+        if constexpr (MASKED) {
+            const float* m = s_m + MS_OFF2 + (2 * r) * MS_L2 + 2 * q;
+            s_m[MS_OFF3 + tid] = pool4(m[0], m[1], m[MS_L2], m[MS_L2 + 1]);
+        }
     }
     __syncthreads();
     // ---- C: the coarse pixels; lanes along coarse rows, which the transposed convention makes the source's columns
@@ -171,6 +199,8 @@ __global__ __launch_bounds__(MS_THREADS) void ms_loss_tile_kernel(const MsArgs p
             const float* ps = (l == 1 ? p.psrc[0] : (l == 2 ? p.psrc[1] : p.psrc[2])) + (int64_t)n * Hsl * Wsl * C;
             const float* pt = (l == 1 ? p.ptgt[0] : (l == 2 ? p.ptgt[1] : p.ptgt[2])) + (((int64_t)n * Hl + ci) * Wl + cj) * C;
             const float2 fl = s_f[off + r * nl + q];
+            [[maybe_unused]] float ml = 1.f;                // m_l of this coarse pixel
+            if constexpr (MASKED) ml = s_m[off + r * nl + q];
             const float x = fl.x * inv_f + (float)ci, y = fl.y * inv_f + (float)cj;
             const bool valid = x > -1.0f && y > -1.0f && x < (float)Wsl && y < (float)Hsl;
             const float fxf = floorf(x), fyf = floorf(y);
@@ -192,11 +222,13 @@ __global__ __launch_bounds__(MS_THREADS) void ms_loss_tile_kernel(const MsArgs p
                 float gc;
                 if (p.kind == 2) { s += (double)(d * d); gc = d * gscale; }
                 else { s += (double)fabsf(d); gc = ((d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f)) * gscale; }
+                if constexpr (MASKED) gc = gc * ml;         // the mask multiplies last
                 const float gx = gc * (dy * (icf - iff) + (1.0f - dy) * (icc - ifc));
                 const float gy = gc * (dx * (ifc - iff) + (1.0f - dx) * (icc - icf));
                 g.x += valid ? gx : 0.f;
                 g.y += valid ? gy : 0.f;
             }
+            if constexpr (MASKED) s = (double)ml * s;
             if (l == 1) sums[0] += s; else if (l == 2) sums[1] += s; else sums[2] += s;
         }
         s_g[off + r * nl + q] = g;
@@ -271,9 +303,9 @@ int ms_launch_pyramid(const MsArgs& p, int grid, hipStream_t s) {
     ms_pyramid_kernel<C><<<grid, MS_THREADS, 0, s>>>(p);
     return launched("ms_pyramid_kernel");
 }
-template <int C>
+template <int C, bool MASKED>
 int ms_launch_tile(const MsArgs& p, int grid, hipStream_t s) {
-    ms_loss_tile_kernel<C><<<grid, MS_THREADS, 0, s>>>(p);
+    ms_loss_tile_kernel<C, MASKED><<<grid, MS_THREADS, 0, s>>>(p);
     return launched("ms_loss_tile_kernel");
 }
 
@@ -282,17 +314,12 @@ int ms_launch_tile(const MsArgs& p, int grid, hipStream_t s) {
 
 using namespace mv3d;
 
-extern "C" {
-
-size_t mv3d_multiscale_warp_loss_workspace_bytes(int N, int H, int W, int Hs, int Ws, int C, int levels) {
-    return ms_shape_ok(N, H, W, Hs, Ws, C, levels) ? ms_layout(N, H, W, Hs, Ws, C, levels).total : 0;
-}
-
-int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
-                              const void* target, int target_ld, int levels, const float* level_weights, int kind, void* loss_accum,
-                              void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    const char* fn = "mv3d_multiscale_warp_loss";
+// Both entries: `mask` is null for mv3d_multiscale_warp_loss (fn names the entry in the messages).
+template <bool MASKED>
+static int ms_entry(const char* fn, int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
+                    const void* target, int target_ld, const void* mask, int mask_ld, int levels, const float* level_weights, int kind,
+                    void* loss_accum, void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
+                    size_t workspace_bytes, void* stream) {
     if (N < 1) return fail(MV3D_E_INVAL, "%s: N (%d) must be at least 1", fn, N);
     if (C < 1 || C > 4) return fail(MV3D_E_INVAL, "%s: C (%d) outside 1..4", fn, C);
     if (levels < 1 || levels > MS_LEVELS) return fail(MV3D_E_INVAL, "%s: levels (%d) outside 1..%d", fn, levels, MS_LEVELS);
@@ -309,9 +336,11 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
     if (src_ld < C) return fail(MV3D_E_INVAL, "%s: src_ld (%d) smaller than C (%d)", fn, src_ld, C);
     if (flow_ld < 2) return fail(MV3D_E_INVAL, "%s: flow_ld (%d) smaller than 2", fn, flow_ld);
     if (target_ld < C) return fail(MV3D_E_INVAL, "%s: target_ld (%d) smaller than C (%d)", fn, target_ld, C);
+    if (MASKED && mask_ld < 1) return fail(MV3D_E_INVAL, "%s: mask_ld (%d) smaller than 1", fn, mask_ld);
     if (grad_ld < 2) return fail(MV3D_E_INVAL, "%s: grad_ld (%d) smaller than 2", fn, grad_ld);
     {   // the largest element index of any operand, formed in int64 by the kernels
-        const int ld = flow_ld > grad_ld ? (flow_ld > target_ld ? flow_ld : target_ld) : (grad_ld > target_ld ? grad_ld : target_ld);
+        int ld = flow_ld > grad_ld ? (flow_ld > target_ld ? flow_ld : target_ld) : (grad_ld > target_ld ? grad_ld : target_ld);
+        if (MASKED && mask_ld > ld) ld = mask_ld;
         if ((double)N * (double)H * (double)W * (double)ld >= 4.0e18 || (double)N * (double)Hs * (double)Ws * (double)src_ld >= 4.0e18)
             return fail(MV3D_E_INVAL, "%s: N (%d) images at these pixel strides overflow the element index", fn, N);
     }
@@ -319,21 +348,24 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
     if (int rc = check_grad_accumulate(fn, grad_accumulate)) return rc;
     if (pyramid_ready != 0 && pyramid_ready != 1) return fail(MV3D_E_INVAL, "%s: pyramid_ready (%d) must be 0 or 1", fn, pyramid_ready);
     if (int rc = check_not_null(fn, {{"src", src}, {"flow", flow}, {"target", target}, {"level_weights", level_weights}})) return rc;
+    if (MASKED)
+        if (int rc = check_not_null(fn, {{"mask", mask}})) return rc;
     for (int l = 0; l < levels; ++l)
         if (!std::isfinite(level_weights[l]))
             return fail(MV3D_E_INVAL, "%s: level_weights[%d] (%g) must be finite", fn, l, (double)level_weights[l]);
     if (!loss_accum && !grad) return fail(MV3D_E_INVAL, "%s: loss_accum and grad are both null", fn);
     if (level_values && !loss_accum) return fail(MV3D_E_INVAL, "%s: level_values without loss_accum", fn);
     const MsLayout lay = ms_layout(N, H, W, Hs, Ws, C, levels);
-    if (int rc = check_buffers(fn, "src, flow, target, loss_accum, level_values or grad",
-                               (uintptr_t)src | (uintptr_t)flow | (uintptr_t)target | (uintptr_t)loss_accum | (uintptr_t)level_values |
-                               (uintptr_t)grad, workspace, workspace_bytes, lay.total)) return rc;
+    if (int rc = check_buffers(fn, MASKED ? "src, flow, target, mask, loss_accum, level_values or grad"
+                                          : "src, flow, target, loss_accum, level_values or grad",
+                               (uintptr_t)src | (uintptr_t)flow | (uintptr_t)target | (uintptr_t)mask | (uintptr_t)loss_accum |
+                               (uintptr_t)level_values | (uintptr_t)grad, workspace, workspace_bytes, lay.total)) return rc;
 
     MsArgs p = {};
-    p.src = (const float*)src; p.flow = (const float*)flow; p.target = (const float*)target;
+    p.src = (const float*)src; p.flow = (const float*)flow; p.target = (const float*)target; p.mask = (const float*)mask;
     p.part = (double*)workspace; p.loss = (float*)loss_accum; p.level_values = (float*)level_values; p.grad = (float*)grad;
     p.N = N; p.H = H; p.W = W; p.Hs = Hs; p.Ws = Ws; p.levels = levels; p.kind = kind;
-    p.src_ld = src_ld; p.flow_ld = flow_ld; p.target_ld = target_ld; p.grad_ld = grad_ld;
+    p.src_ld = src_ld; p.flow_ld = flow_ld; p.target_ld = target_ld; p.mask_ld = mask_ld; p.grad_ld = grad_ld;
     p.accumulate = grad_accumulate;
     // mv3d_loss_overwrite_next(): consumed by a call that writes the loss word (kept by a recorded one); a gradient-only call
     // is no loss entry and leaves it pending
@@ -373,17 +405,17 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
     }
     {
         // algorithmic bytes: the flow once, the gradient written once (and read once when it accumulates), both pyramids once, the
-        // tile sums.  FLOPs: 12 per flow pixel to pool and combine, ~(30 + 20 C) per coarse pixel
+        // tile sums (and the mask's 4 B per flow pixel).  FLOPs: 12 per flow pixel to pool and combine, ~(30 + 20 C) per coarse pixel
         const double grad_bytes = grad ? (grad_accumulate ? 16.0 : 8.0) : 0.0;
         const double coarse = px * (levels == 1 ? 0.25 : (levels == 2 ? 0.3125 : 0.328125));
-        const OpInfo info{intern_label("multiscale_loss_tile"), px * 12.0 + coarse * (30.0 + 20.0 * C),
-                          px * (8.0 + grad_bytes) + pyr_px * 4.0 * C + (loss_accum ? (double)tiles * 24.0 : 0.0)};
+        const OpInfo info{intern_label(MASKED ? "multiscale_loss_masked_tile" : "multiscale_loss_tile"), px * 12.0 + coarse * (30.0 + 20.0 * C),
+                          px * (8.0 + grad_bytes + (MASKED ? 4.0 : 0.0)) + pyr_px * 4.0 * C + (loss_accum ? (double)tiles * 24.0 : 0.0)};
         rc = dispatch(stream, info, [=](hipStream_t s) {
             switch (C) {
-                case 1: return ms_launch_tile<1>(p, tiles, s);
-                case 2: return ms_launch_tile<2>(p, tiles, s);
-                case 3: return ms_launch_tile<3>(p, tiles, s);
-                default: return ms_launch_tile<4>(p, tiles, s);
+                case 1: return ms_launch_tile<1, MASKED>(p, tiles, s);
+                case 2: return ms_launch_tile<2, MASKED>(p, tiles, s);
+                case 3: return ms_launch_tile<3, MASKED>(p, tiles, s);
+                default: return ms_launch_tile<4, MASKED>(p, tiles, s);
             }
         });
     }
@@ -393,6 +425,30 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
         ms_loss_final_kernel<<<1, MS_THREADS, 0, s>>>(p);
         return launched("ms_loss_final_kernel");
     });
+}
+
+extern "C" {
+
+size_t mv3d_multiscale_warp_loss_workspace_bytes(int N, int H, int W, int Hs, int Ws, int C, int levels) {
+    return ms_shape_ok(N, H, W, Hs, Ws, C, levels) ? ms_layout(N, H, W, Hs, Ws, C, levels).total : 0;
+}
+
+int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
+                              const void* target, int target_ld, int levels, const float* level_weights, int kind, void* loss_accum,
+                              void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return ms_entry<false>("mv3d_multiscale_warp_loss", N, H, W, Hs, Ws, C, src, src_ld, flow, flow_ld, target, target_ld, nullptr, 1, levels,
+                           level_weights, kind, loss_accum, level_values, grad, grad_ld, grad_accumulate, pyramid_ready, workspace,
+                           workspace_bytes, stream);
+}
+
+int mv3d_multiscale_warp_loss_masked(int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
+                                     const void* target, int target_ld, const void* mask, int mask_ld, int levels,
+                                     const float* level_weights, int kind, void* loss_accum, void* level_values, void* grad, int grad_ld,
+                                     int grad_accumulate, int pyramid_ready, void* workspace, size_t workspace_bytes, void* stream) {
+    return ms_entry<true>("mv3d_multiscale_warp_loss_masked", N, H, W, Hs, Ws, C, src, src_ld, flow, flow_ld, target, target_ld, mask, mask_ld,
+                          levels, level_weights, kind, loss_accum, level_values, grad, grad_ld, grad_accumulate, pyramid_ready, workspace,
+                          workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -414,11 +414,13 @@ class SmoothTerm(LossTerm):
 class MultiscaleTerm(LossTerm):
     """The multi-scale photometric loss (mv3d_multiscale_warp_loss) of the flow a, which warps `src` onto the target b over `levels`
     pyramid levels with weights `level_weights` and pixel loss `pixel_kind` (LOSS_L1 / LOSS_L2); neither image is differentiated.
-    The workspace holds the tile sums and both pyramids: a call without the value is the reverse-pass call, which reuses them."""
+    The workspace holds the tile sums and both pyramids: a call without the value is the reverse-pass call, which reuses them.
+    With a one-channel mask over the flow's grid both calls are the masked form's (mv3d_multiscale_warp_loss_masked; the same
+    workspace: the mask is pooled inside the tile launch)."""
     kind, order, on_flow = LOSS_MULTISCALE, 4, True
 
-    def __init__(self, a, b, src, levels, level_weights, pixel_kind=LOSS_L2):
-        LossTerm.__init__(self, a, b)
+    def __init__(self, a, b, src, levels, level_weights, pixel_kind=LOSS_L2, mask=None):
+        LossTerm.__init__(self, a, b, mask)
         self.src, self.levels, self.level_weights, self.pixel_kind = src, int(levels), tuple(float(v) for v in level_weights), pixel_kind
 
     def workspace_bytes(self, lib):
@@ -427,8 +429,14 @@ class MultiscaleTerm(LossTerm):
                              "what mv3d_multiscale_warp_loss takes" % (self.a.shape, self.src.shape, self.levels))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b, s = self.a, self.b, self.src
+        a, b, s, m = self.a, self.b, self.src, self.mask
         weights = (C.c_float * self.levels)(*[float(w) * v for v in self.level_weights])
+        if m is not None:
+            g.lib.multiscale_warp_loss_masked(*a.shape[:3], s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld,
+                                              self.levels, weights, self.pixel_kind, g.loss_buf.data_ptr() if value else None, None,
+                                              a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, 0 if value else 1,
+                                              self.ws.data_ptr(), self.ws.numel(), g.stream)
+            return
         g.lib.multiscale_warp_loss(*a.shape[:3], s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, self.levels, weights,
                                    self.pixel_kind, g.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None, a.ld,
                                    1 if (grad and accumulate) else 0, 0 if value else 1, self.ws.data_ptr(), self.ws.numel(), g.stream)
@@ -1074,7 +1082,8 @@ class Graph:
             if t.mask is not None:
                 # A masked loss fuses only when the mask is the occlusion mask of the resampler's own flow: the fused launch then
                 # makes it (mv3d_warp_resample_occlusion_loss).  The mask node has to come behind the resampler, so that nothing in
-                # front of the fused launch can have read the mask.
+                # front of the fused launch can have read the mask.  (A masked multi-scale term is a second reader of the mask: it
+                # sits on the flow, not on gen, and its launches go with the losses behind every node's, so the head stays fused.)
                 occl = t.mask.producer
                 if not (isinstance(occl, OcclusionMaskNode) and occl.mask is t.mask and occl.flow is n.flow and occl.fused_into is None
                         and self.nodes.index(occl) > self.nodes.index(n)):

@@ -693,6 +693,12 @@ def _multiscale_shapes(src, flow, target, levels):
             raise ValueError("multiscale_warp_loss: %s (%d) must be a positive multiple of 2^levels = %d" % (name, v, 1 if name == 'N' else f))
 
 
+def _multiscale_mask_shape(mask, flow):
+    """Checks the mask's shape [N,H,W,1] over the flow's N, H, W."""
+    if tuple(mask) != tuple(flow[:3]) + (1,):
+        raise ValueError("multiscale_warp_loss: mask must be [N,H,W,1] over the flow's %s, got %s" % (tuple(flow[:3]), tuple(mask)))
+
+
 def _pool2(x):
     """One pyramid step over [N,H,W,C]: 0.25 * ((p00 + p01) + (p10 + p11)) of every 2 x 2 block, in x's dtype."""
     return x.dtype.type(0.25) * ((x[:, 0::2, 0::2] + x[:, 0::2, 1::2]) + (x[:, 1::2, 0::2] + x[:, 1::2, 1::2]))
@@ -717,7 +723,7 @@ def _bilinear_taps(data, x, y):
     return valid, dx, dy, tap(fy, fx), tap(fy + 1, fx + 1), tap(fy + 1, fx), tap(fy, fx + 1)
 
 
-def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kind=2, dtype=np.float64):
+def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kind=2, dtype=np.float64, mask=None):
     """(value, grad, level_values) of the multi-scale photometric loss of a flow [N,H,W,2] that warps src [N,Hs,Ws,C] onto target
     [N,H,W,C]: value = sum_l w_l T_l, a scalar of `dtype`; grad = d value / d flow, [N,H,W,2]; level_values = [T_1 .. T_L], the
     unweighted terms; every step in `dtype` arithmetic.  At float32 this states mv3d_multiscale_warp_loss's own operation order
@@ -734,11 +740,23 @@ def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kin
       G_l[..., 0] = sum_c g (dy (icf - iff) + (1-dy) (icc - ifc)),  G_l[..., 1] = sum_c g (dx (ifc - iff) + (1-dx) (icc - icf)),
                channels added in index order, 0 where the point is not valid
       grad[n,i,j] = (G_1[n, i>>1, j>>1] + G_2[n, i>>2, j>>2]) + G_3[n, i>>3, j>>3]      (1 / f^2 from the mean, 1 / f from the scaling)
-    src and target are not differentiated.  gen_l == pool_l(target) at every level gives exactly (0, zeros, zeros)."""
+    src and target are not differentiated.  gen_l == pool_l(target) at every level gives exactly (0, zeros, zeros).
+
+    mask (optional): [N,H,W,1] over the flow's grid, not differentiated; the statement of mv3d_multiscale_warp_loss_masked:
+      m_l    = pool_l(mask), the same pooling, level by level: a coarse pixel counts by its visible share, a 0/1 mask pools exactly
+      T_l    = (1 / (N H_l W_l)) sum over (n,I,J) of m_l sum_c phi(d): the count stays that of the unmasked term, as in the masked
+               census and SSIM terms
+      g      = (d s_l) m_l (kind 2) or (sign(d) s_l) m_l (kind 1): s_l unchanged, the mask multiplies last; G_l and grad as above
+    A mask of ones gives the unmasked result bit for bit, a mask of zeros exact zeros, gen_l == pool_l(target) exactly 0 under any
+    mask; value and gradient are linear in the mask.  mask=None is the unmasked code, untouched."""
     dtype = np.dtype(dtype).type
     levels, weights, kind = _multiscale_scalars(levels, level_weights, kind)
     s, fl, t = (np.asarray(v).astype(dtype) for v in (src, flow, target))
     _multiscale_shapes(s.shape, fl.shape, t.shape, levels)
+    ml = None
+    if mask is not None:
+        ml = np.asarray(mask).astype(dtype)
+        _multiscale_mask_shape(ml.shape, fl.shape)
     n, h, w, _ = fl.shape
     one, zero = dtype(1), dtype(0)
     value, grad, level_values = 0.0, None, []
@@ -755,6 +773,9 @@ def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kin
         count = float(n) * hl * wl
         scale = dtype(weights[l - 1] * (2.0 if kind == 2 else 1.0) / count / float(f * f * f))
         phi, g = (d * d, d * scale) if kind == 2 else (np.abs(d), np.sign(d) * scale)
+        if ml is not None:
+            ml = _pool2(ml)
+            phi, g = phi * ml, g * ml
         T = dtype(float(phi.sum(dtype=dtype)) / count)
         level_values.append(T)
         value += weights[l - 1] * float(T)
@@ -770,12 +791,14 @@ def multiscale_warp_loss_host(src, flow, target, levels, level_weights=None, kin
     return dtype(value), grad, np.array(level_values, dtype)
 
 
-def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, grad=None, accumulate=False, stream=None):
+def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, grad=None, accumulate=False, stream=None, mask=None):
     """mv3d_multiscale_warp_loss on device memory: the value of multiscale_warp_loss_host and the unweighted T_l, and optionally
     the gradient with respect to the flow.  src / flow / target: graph Tensors (channel views included) or torch device tensors,
     float32 [N,Hs,Ws,C] / [N,H,W,2] / [N,H,W,C].  grad: an optional float32 device tensor of the flow's shape with one pixel stride
     (a channel slice of a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream`
-    (default: torch's current stream of the operands' device).  Returns (value, level_values): a 0-d and a [levels] device tensor.
+    (default: torch's current stream of the operands' device).  mask (optional): a graph Tensor or torch device tensor, float32
+    [N,H,W,1] over the flow's grid on the flow's device (a channel of a wider tensor works): mv3d_multiscale_warp_loss_masked, the
+    masked form multiscale_warp_loss_host states.  Returns (value, level_values): a 0-d and a [levels] device tensor.
     Raises ValueError on what the C entry would refuse."""
     import ctypes
     import torch
@@ -787,6 +810,9 @@ def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, 
     _multiscale_shapes(shape_s, shape, shape_t, levels)
     if not _same_device(dev_s, dev) or not _same_device(dev_t, dev):
         raise ValueError("multiscale_warp_loss: src on %s, target on %s, flow on %s" % (dev_s, dev_t, dev))
+    pm, m_ld = None, 1
+    if mask is not None:
+        pm, m_ld = _mask_operand('multiscale_warp_loss', mask, shape, dev)
     dev = torch.device(dev)
     if dev.type != 'cuda':
         raise _lib.Mv3dError("multiscale_warp_loss runs on the GPU (operands are on %s); multiscale_warp_loss_host is the numpy form" % dev)
@@ -805,6 +831,11 @@ def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, 
     ws = _workspace(dev, nbytes)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if mask is not None:
+        lib.multiscale_warp_loss_masked(n, h, w, shape_s[1], shape_s[2], shape_t[3], ps, s_ld, pf, f_ld, pt, t_ld, pm, m_ld, levels,
+                                        (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
+                                        1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)
+        return out, level_values
     lib.multiscale_warp_loss(n, h, w, shape_s[1], shape_s[2], shape_t[3], ps, s_ld, pf, f_ld, pt, t_ld, levels,
                              (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
                              1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)

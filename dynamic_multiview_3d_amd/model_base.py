@@ -238,8 +238,8 @@ def occlusion_from_conf(conf):
     its loss, or 'mask': it loses it, UnFlow's choice).  The switch needs conf['pair_swap'] (pair_swap.py): the mask comes from the
     forward-backward residual of sample n against sample n + batch_size / 2.  Combined with conf['ssim_loss_weight'] or
     conf['census_loss_weight'] the switch is refused unless conf['occlusion_mask_image_terms'] opts into their masked forms
-    (occlusion_image_terms_from_conf); the multi-scale term has no masked form, so conf['multiscale_loss_levels'] is refused
-    either way.  Raises ValueError on a non-bool switch, a bool, negative or non-finite alpha1, an alpha2 <= 0, an unknown
+    (occlusion_image_terms_from_conf), and combined with conf['multiscale_loss_levels'] unless conf['occlusion_mask_multiscale']
+    opts into the masked multi-scale term (occlusion_multiscale_from_conf).  Raises ValueError on a non-bool switch, a bool, negative or non-finite alpha1, an alpha2 <= 0, an unknown
     conf['occlusion_outside'], a missing conf['pair_swap'] or one of those combinations, before any device work."""
     from .pair_swap import pair_swap_from_conf
     on = conf.get('occlusion_mask')
@@ -274,8 +274,9 @@ def occlusion_from_conf(conf):
     if census_from_conf(conf)[0] > 0 and not image_terms:
         raise ValueError("conf['occlusion_mask'] does not combine with conf['census_loss_weight']: the census loss has no masked form "
                          "unless conf['occlusion_mask_image_terms'] = True asks for it")
-    if multiscale_loss_from_conf(conf)[0] > 0:
-        raise ValueError("conf['occlusion_mask'] does not combine with conf['multiscale_loss_levels']: the multi-scale loss has no masked form")
+    if multiscale_loss_from_conf(conf)[0] > 0 and not _occlusion_multiscale_switch(conf):
+        raise ValueError("conf['occlusion_mask'] does not combine with conf['multiscale_loss_levels']: the multi-scale loss has no masked form "
+                         "unless conf['occlusion_mask_multiscale'] = True asks for it")
     return alphas[0], alphas[1], outside == 'keep'
 
 
@@ -299,6 +300,29 @@ def occlusion_image_terms_from_conf(conf):
     if on and occlusion_from_conf(conf) is None:
         raise ValueError("conf['occlusion_mask_image_terms'] needs conf['occlusion_mask'] = True: the masked SSIM and census "
                          "terms take the occlusion_mask of the head loss")
+    return on
+
+
+def _occlusion_multiscale_switch(conf):
+    """conf['occlusion_mask_multiscale'] as a bool (absent, None or False = off); ValueError on anything that is not a bool."""
+    on = conf.get('occlusion_mask_multiscale')
+    if on is not None and not isinstance(on, (bool, np.bool_)):
+        raise ValueError("conf['occlusion_mask_multiscale'] must be True or False (or None for off), got %r" % (on,))
+    return bool(on)
+
+
+def occlusion_multiscale_from_conf(conf):
+    """True when the multi-scale term takes the head's occlusion mask: conf['occlusion_mask_multiscale'] (absent, None or False =
+    off, which leaves every conf behaving, raising and recording as it did without the key).  True needs conf['occlusion_mask']:
+    multiscale_term() then passes the mask head_loss() created for its flow, pooled level by level like the images (UnFlow, DDFlow
+    and ARFlow apply the forward-backward mask at every pyramid level), and conf['occlusion_mask'] combines with
+    conf['multiscale_loss_levels'].  With the multi-scale switch off the key changes nothing.  The smoothness and consistency
+    terms stay unmasked.  Raises ValueError on a value that is not a bool (with the switches off as well) and on True without
+    conf['occlusion_mask'], before any device work."""
+    on = _occlusion_multiscale_switch(conf)
+    if on and occlusion_from_conf(conf) is None:
+        raise ValueError("conf['occlusion_mask_multiscale'] needs conf['occlusion_mask'] = True: the masked multi-scale term takes "
+                         "the occlusion_mask of the head loss")
     return on
 
 
@@ -361,6 +385,8 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['occlusion_mask']" % type(self).__name__)
         if occlusion_image_terms_from_conf(self.conf) and not self.supports_occlusion_mask:
             raise ValueError("%s does not support conf['occlusion_mask_image_terms']" % type(self).__name__)
+        if occlusion_multiscale_from_conf(self.conf) and not self.supports_occlusion_mask:
+            raise ValueError("%s does not support conf['occlusion_mask_multiscale']" % type(self).__name__)
 
     def _note_term(self, attr, entry):
         """One more entry of a per-term list that evaluate() reports from (_report); the list exists only once a term was added."""
@@ -428,13 +454,25 @@ class ModelBase(object):
         """multiscale_photometric_loss(flow, src, target) with the levels, weights and kind of conf['multiscale_loss_*'] on one flow
         head, or 0 when the switch is off (the graph then records exactly what it recorded without the keys).  Raises ValueError
         for an image size that is no multiple of 2^levels.  evaluate() reports the unweighted level terms as '<name>/photo_x2',
-        '<name>/photo_x4', '<name>/photo_x8'."""
+        '<name>/photo_x4', '<name>/photo_x8'.  With conf['occlusion_mask_multiscale'] the term takes the occlusion mask head_loss()
+        made for this flow (multiscale_photometric_loss(..., mask=)); '<name>/photo_x*' stay the unmasked figures, comparable across
+        runs, and '<name>/photo_x2_masked', '_x4_masked', '_x8_masked' are the unweighted level terms as trained."""
         from .tf_utils import multiscale_photometric_loss
         levels, weights, kind = multiscale_loss_from_conf(self.conf)
         if levels == 0:
             return 0
+        mask = None
+        if occlusion_multiscale_from_conf(self.conf):
+            for term in getattr(self, 'occlusion_terms', []):
+                if term[1] is flow:
+                    mask = term[2]
+            if mask is None:
+                raise RuntimeError("multiscale_term: conf['occlusion_mask_multiscale'] is on, but head_loss() made no occlusion mask "
+                                   "for this flow (call head_loss() first)")
         self._note_term('multiscale_terms', (name, flow, src, target, levels, kind))
-        return multiscale_photometric_loss(flow, src, target, levels, weights, kind)
+        if mask is not None:
+            self._note_term('masked_multiscale_terms', (name, flow, src, target, levels, kind, mask))
+        return multiscale_photometric_loss(flow, src, target, levels, weights, kind, mask=mask)
 
     def flow_smoothness_term(self, flow, guide, name='flow'):
         """conf['flow_smoothness_weight'] * flow_smoothness_loss(flow, guide, edge, eps) on one flow head, or 0 when the switch is
@@ -644,6 +682,11 @@ class ModelBase(object):
             return (levels, into(lambda loss: metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1]),
                     lambda loss: metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None, ms_kind[kind])[2],
                     means(*['%s/photo_x%d' % (name, 2 << l) for l in range(levels)]))
+        def masked_multiscale(name, flow, src, target, levels, kind, mask):     # the masked level terms as trained
+            return (levels, into(lambda loss: metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind], mask=mask)[1]),
+                    lambda loss: metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None, ms_kind[kind],
+                                                                   mask=mask.numpy())[2],
+                    means(*['%s/photo_x%d_masked' % (name, 2 << l) for l in range(levels)]))
         def census(name, pred, target, max_val, radius, eps):
             return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps)),
                     lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0]),
@@ -668,7 +711,8 @@ class ModelBase(object):
         report = [(1, into(lambda loss: loss), float, means('loss'))] if self.graph.loss_expr is not None else []
         report += [pair(*p) for p in pairs]
         for make, attr in ((smoothness, 'smoothness_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
-                           (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms'), (masked_image, 'masked_image_terms')):
+                           (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms'), (masked_image, 'masked_image_terms'),
+                           (masked_multiscale, 'masked_multiscale_terms')):
             report += [make(*term) for term in getattr(self, attr, [])]
         return report
 

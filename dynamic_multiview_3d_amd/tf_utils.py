@@ -195,13 +195,16 @@ def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
     return ScalarExpr([(1.0, SmoothTerm(flow, guide, edge_alpha, eps))])
 
 
-def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=None, kind='l2'):
+def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=None, kind='l2', mask=None):
     """Coarse-to-fine photometric loss of a flow field [N,H,W,2] (mv3d_multiscale_warp_loss; metrics.multiscale_warp_loss_host
     states the definition): sum over the levels l = 1..levels of level_weights[l-1] times the euclidean_loss ('l2') or l1_loss
     ('l1') between the 2^l-times pooled src_img, warped by the pooled and rescaled flow, and the pooled target.  level_weights: a
     list of `levels` finite weights (default: all 1).  The flow must be differentiated (it is usually an intermediate tensor: its
     gradient from the sampler and this term's are added); the images must not be.  Every side of src_img [N,Hs,Ws,C] and target
-    [N,H,W,C], C <= 4, must be a multiple of 2^levels.  Masked and scaled operands are not supported."""
+    [N,H,W,C], C <= 4, must be a multiple of 2^levels.  Masked and scaled operands are not supported.  mask (optional): a graph
+    tensor [N,H,W,1] over the flow's grid that is not differentiated, usually occlusion_mask(flow); it is pooled like the images,
+    every coarse pixel is weighed by its pooled mask and the means keep their counts (mv3d_multiscale_warp_loss_masked;
+    metrics.multiscale_warp_loss_host states the definition)."""
     from .metrics import _multiscale_scalars, _multiscale_shapes
     for v in (flow, src_img, target):
         if isinstance(v, (_Masked, _Scaled)):
@@ -218,7 +221,8 @@ def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=N
         raise ValueError("multiscale_photometric_loss: the flow is not differentiated (nothing to learn)")
     if src_img.requires_grad or target.requires_grad:
         raise NotImplementedError("multiscale_photometric_loss: the images are not differentiated; they must not require a gradient")
-    return ScalarExpr([(1.0, MultiscaleTerm(flow, target, src_img, levels, weights, LOSS_L2 if kind == 'l2' else LOSS_L1))])
+    mask = _image_mask('multiscale_photometric_loss', mask, flow)
+    return ScalarExpr([(1.0, MultiscaleTerm(flow, target, src_img, levels, weights, LOSS_L2 if kind == 'l2' else LOSS_L1, mask))])
 
 
 def flow_consistency_loss(flow, eps=1e-3):

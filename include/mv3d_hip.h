@@ -495,6 +495,25 @@ int mv3d_multiscale_warp_loss(int N, int H, int W, int Hs, int Ws, int C, const 
                               const void* target, int target_ld, int levels, const float* level_weights, int kind, void* loss_accum,
                               void* level_values, void* grad, int grad_ld, int grad_accumulate, int pyramid_ready, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* The masked form: mask [N,H,W,1] fp32 over the flow's grid with pixel stride mask_ld >= 1 (a channel of a wider tensor works);
+ * it is not differentiated.  m_l = pool_l(mask), the pooling of the images and the flow, so a coarse pixel counts by its visible
+ * share and a 0/1 mask pools exactly.
+ *   T_l  = (1 / (N H_l W_l)) * sum over (n,I,J) of m_l(n,I,J) * sum_c phi(d_c): the count stays that of the unmasked term (as in
+ *          mv3d_census_loss_masked and mv3d_ssim_loss_masked); a coarse pixel's channel sum s is formed in double as in the
+ *          unmasked entry and the level sum adds (double)m_l * s
+ *   dgen = (d_c * s_l) * m_l (kind 2) or (sign(d_c) * s_l) * m_l (kind 1): s_l unchanged, the mask multiplies last; G_l and grad
+ *          follow from it as above
+ * A mask of ones gives the value, level values and gradient of mv3d_multiscale_warp_loss bit for bit, a mask of zeros +0 and a
+ * gradient of zeros, gen_l == pool_l(target) exactly 0 under any mask; value and gradient are linear in the mask.  The mask is
+ * pooled inside the tile launch, beside the flow: the pyramid launch, the workspace (mv3d_multiscale_warp_loss_workspace_bytes(),
+ * the same layout) and pyramid_ready mean what they mean above, and a pyramid_ready call reads the mask again.  Launches:
+ * multiscale_pyramid (unless pyramid_ready), multiscale_loss_masked_tile, multiscale_loss_final (only with loss_accum).
+ * Everything else, mv3d_loss_overwrite_next() included, is as above.  MV3D_E_INVAL in addition: mask_ld < 1; mask NULL or not
+ * 4-byte aligned. */
+int mv3d_multiscale_warp_loss_masked(int N, int H, int W, int Hs, int Ws, int C, const void* src, int src_ld, const void* flow, int flow_ld,
+                                     const void* target, int target_ld, const void* mask, int mask_ld, int levels,
+                                     const float* level_weights, int kind, void* loss_accum, void* level_values, void* grad, int grad_ld,
+                                     int grad_accumulate, int pyramid_ready, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- forward-backward flow consistency over pair-swapped batches: value and gradient with respect to the flow --------------
  * flow [N,H,W,2] fp32 with pixel stride flow_ld (a channel-slice view works), N even, H == W >= 2.  The second half of the batch
