@@ -28,7 +28,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, loss_calls
 from ._lib import ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH
 
 _current = []
@@ -301,6 +301,11 @@ class ScalarExpr:
 LOSS_L1, LOSS_L2, LOSS_SSIM, LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CENSUS, LOSS_CONSIST = 1, 2, 3, 4, 5, 6, 7
 
 
+def _at(t):
+    """(address, pixel stride) of a Tensor for loss_calls, or None for an absent operand."""
+    return (t.ptr, t.ld) if t is not None else None
+
+
 class LossTerm:
     """One term of the loss on the differentiated tensor a against b.  A class states its `kind` (LOSS_*), its `order` (the terms
     of a step are launched in this order: Graph._emit_losses) and `on_flow`: a term on a flow, usually an INTERMEDIATE tensor whose
@@ -324,8 +329,16 @@ class LossTerm:
 
     def launch(self, g, w, value, grad, accumulate):
         """Record the term's library call at weight w: the value into the loss word and / or the gradient stored into (or, with
-        accumulate, added onto) a's gradient buffer."""
+        accumulate, added onto) a's gradient buffer.  The terms with an eager twin in metrics.py call through loss_calls, which
+        owns the argument layout and the choice of the masked entry."""
         raise NotImplementedError
+
+    def _grad_at(self, grad):
+        """(address, pixel stride) of a's gradient for loss_calls, or None without `grad`."""
+        return (self.a.grad_ptr, self.a.ld) if grad else None
+
+    def _ws_at(self):
+        return self.ws.data_ptr(), self.ws.numel()
 
 
 class PixelTerm(LossTerm):
@@ -353,18 +366,12 @@ class SsimTerm(LossTerm):
         self.max_val = float(max_val)
 
     def workspace_bytes(self, lib):
-        size = lib.ssim_loss_workspace_bytes if self.mask is None else lib.ssim_loss_masked_workspace_bytes
-        return self._nonzero(size(*self.a.shape),
+        return self._nonzero(loss_calls.ssim_workspace_bytes(lib, self.a.shape, self.mask is not None),
                              "ssim_loss: operands of shape %s are outside what mv3d_ssim_loss takes" % (self.a.shape,))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b, m = self.a, self.b, self.mask
-        if m is not None:
-            g.lib.ssim_loss_masked(*a.shape, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld, self.max_val, float(w), g.loss_buf.data_ptr(),
-                                   a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
-            return
-        g.lib.ssim_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.max_val, float(w), g.loss_buf.data_ptr(),
-                        a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+        loss_calls.ssim(g.lib, self.a.shape, _at(self.a), _at(self.b), _at(self.mask), self.max_val, w, g.loss_buf.data_ptr(),
+                        self._grad_at(grad), accumulate, self._ws_at(), g.stream)
 
 
 class CensusTerm(LossTerm):
@@ -377,18 +384,12 @@ class CensusTerm(LossTerm):
         self.max_val, self.radius, self.eps = float(max_val), int(radius), float(eps)
 
     def workspace_bytes(self, lib):
-        return self._nonzero(lib.census_loss_workspace_bytes(*self.a.shape, self.radius),
+        return self._nonzero(loss_calls.census_workspace_bytes(lib, self.a.shape, self.radius),
                              "census_loss: operands of shape %s at radius %d are outside what mv3d_census_loss takes" % (self.a.shape, self.radius))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b, m = self.a, self.b, self.mask
-        if m is not None:
-            g.lib.census_loss_masked(*a.shape, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld, self.radius, self.max_val, self.eps, float(w),
-                                     g.loss_buf.data_ptr(), a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0,
-                                     self.ws.data_ptr(), self.ws.numel(), g.stream)
-            return
-        g.lib.census_loss(*a.shape, a.ptr, a.ld, b.ptr, b.ld, self.radius, self.max_val, self.eps, float(w), g.loss_buf.data_ptr(),
-                          a.grad_ptr if grad else None, a.ld, 1 if accumulate else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+        loss_calls.census(g.lib, self.a.shape, _at(self.a), _at(self.b), _at(self.mask), self.radius, self.max_val, self.eps, w,
+                          g.loss_buf.data_ptr(), self._grad_at(grad), accumulate, self._ws_at(), g.stream)
 
 
 class SmoothTerm(LossTerm):
@@ -401,14 +402,14 @@ class SmoothTerm(LossTerm):
         self.edge_alpha, self.eps = float(edge_alpha), float(eps)
 
     def workspace_bytes(self, lib):
-        return self._nonzero(lib.flow_smoothness_workspace_bytes(*self.a.shape[:3]),
+        return self._nonzero(loss_calls.flow_smoothness_workspace_bytes(lib, self.a.shape[:3]),
                              "flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (self.a.shape,))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b = self.a, self.b
-        gp, gc, gld = (b.ptr, b.C, b.ld) if b is not None else (None, 0, 0)
-        g.lib.flow_smoothness(*a.shape[:3], a.ptr, a.ld, gp, gc, gld, self.edge_alpha, self.eps, float(w), g.loss_buf.data_ptr() if value else None,
-                              a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+        b = self.b
+        loss_calls.flow_smoothness(g.lib, self.a.shape[:3], _at(self.a), (b.ptr, b.C, b.ld) if b is not None else None, self.edge_alpha,
+                                   self.eps, w, g.loss_buf.data_ptr() if value else None, self._grad_at(grad), grad and accumulate,
+                                   self._ws_at(), g.stream)
 
 
 class MultiscaleTerm(LossTerm):
@@ -424,22 +425,15 @@ class MultiscaleTerm(LossTerm):
         self.src, self.levels, self.level_weights, self.pixel_kind = src, int(levels), tuple(float(v) for v in level_weights), pixel_kind
 
     def workspace_bytes(self, lib):
-        return self._nonzero(lib.multiscale_warp_loss_workspace_bytes(*self.a.shape[:3], *self.src.shape[1:], self.levels),
+        return self._nonzero(loss_calls.multiscale_workspace_bytes(lib, self.a.shape[:3], self.src.shape[1:], self.levels),
                              "multiscale_photometric_loss: a flow of shape %s over a source of shape %s at %d levels is outside "
                              "what mv3d_multiscale_warp_loss takes" % (self.a.shape, self.src.shape, self.levels))
 
     def launch(self, g, w, value, grad, accumulate):
-        a, b, s, m = self.a, self.b, self.src, self.mask
-        weights = (C.c_float * self.levels)(*[float(w) * v for v in self.level_weights])
-        if m is not None:
-            g.lib.multiscale_warp_loss_masked(*a.shape[:3], s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, m.ptr, m.ld,
-                                              self.levels, weights, self.pixel_kind, g.loss_buf.data_ptr() if value else None, None,
-                                              a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, 0 if value else 1,
-                                              self.ws.data_ptr(), self.ws.numel(), g.stream)
-            return
-        g.lib.multiscale_warp_loss(*a.shape[:3], s.shape[1], s.shape[2], s.C, s.ptr, s.ld, a.ptr, a.ld, b.ptr, b.ld, self.levels, weights,
-                                   self.pixel_kind, g.loss_buf.data_ptr() if value else None, None, a.grad_ptr if grad else None, a.ld,
-                                   1 if (grad and accumulate) else 0, 0 if value else 1, self.ws.data_ptr(), self.ws.numel(), g.stream)
+        loss_calls.multiscale(g.lib, self.a.shape[:3], self.src.shape[1:], _at(self.src), _at(self.a), _at(self.b), _at(self.mask),
+                              self.levels, [float(w) * v for v in self.level_weights], self.pixel_kind,
+                              g.loss_buf.data_ptr() if value else None, None, self._grad_at(grad), grad and accumulate, not value,
+                              self._ws_at(), g.stream)
 
 
 class ConsistTerm(LossTerm):
@@ -452,13 +446,12 @@ class ConsistTerm(LossTerm):
         self.eps = float(eps)
 
     def workspace_bytes(self, lib):
-        return self._nonzero(lib.flow_consistency_workspace_bytes(*self.a.shape[:3]),
+        return self._nonzero(loss_calls.flow_consistency_workspace_bytes(lib, self.a.shape[:3]),
                              "flow_consistency_loss: a flow of shape %s is outside what mv3d_flow_consistency takes" % (self.a.shape,))
 
     def launch(self, g, w, value, grad, accumulate):
-        a = self.a
-        g.lib.flow_consistency(*a.shape[:3], a.ptr, a.ld, self.eps, float(w), g.loss_buf.data_ptr() if value else None, None,
-                               a.grad_ptr if grad else None, a.ld, 1 if (grad and accumulate) else 0, self.ws.data_ptr(), self.ws.numel(), g.stream)
+        loss_calls.flow_consistency(g.lib, self.a.shape[:3], _at(self.a), self.eps, w, g.loss_buf.data_ptr() if value else None, None,
+                                    self._grad_at(grad), grad and accumulate, self._ws_at(), g.stream)
 
 
 FLOW_TERMS = tuple(c.kind for c in LossTerm.__subclasses__() if c.on_flow)      # (LOSS_SMOOTH, LOSS_MULTISCALE, LOSS_CONSIST)

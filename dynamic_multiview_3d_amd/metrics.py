@@ -194,16 +194,68 @@ def _operand(x, what):
     return x.ptr, tuple(x.shape), x.ld, x.graph.device
 
 
+def _same_device(a, b):
+    """A graph Tensor names its device as the graph was given it ('cuda'), a torch tensor with its index ('cuda:0')."""
+    import torch
+    a, b = torch.device(a), torch.device(b)
+    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
+
+
 def _mask_operand(op, mask, shape, dev):
     """(data pointer, pixel stride) of the mask of a masked image loss: a graph Tensor or a torch device tensor [N,H,W,1] over the
-    operands' N, H, W on their device (a channel of a wider tensor works)."""
-    import torch
+    operands' N, H, W on their device (a channel of a wider tensor works); None for no mask."""
+    if mask is None:
+        return None
     pm, shape_m, m_ld, dev_m = _operand(mask, 'mask')
     if shape_m != tuple(shape[:3]) + (1,):
         raise ValueError("%s: mask must be [N,H,W,1] over the operands' %s, got %s" % (op, tuple(shape[:3]), shape_m))
     if not _same_device(dev_m, dev):
         raise ValueError("%s: mask on %s, operands on %s" % (op, dev_m, dev))
     return pm, m_ld
+
+
+# The preamble of the eager wrappers below, in the order each of them takes it: operands, the GPU check, grad, the launch resources.
+def _gpu_device(op, dev, *others):
+    """`dev` as a torch.device; Mv3dError unless it and `others` are GPU devices."""
+    import torch
+    from . import _lib
+    dev = torch.device(dev)
+    if any(torch.device(d).type != 'cuda' for d in (dev,) + others):
+        raise _lib.Mv3dError("%s runs on the GPU (operands are on %s); %s_host is the numpy form" % (op, dev, op))
+    return dev
+
+
+def _image_pair(op, pred, target):
+    """((address, pixel stride) of pred, the same of target, their one shape, their GPU device) of an image operation."""
+    pa, shape, a_ld, dev = _operand(pred, 'pred')
+    pb, shape_b, b_ld, dev_b = _operand(target, 'target')
+    if shape != shape_b:
+        raise ValueError("%s: pred %s and target %s differ in shape" % (op, shape, shape_b))
+    return (pa, a_ld), (pb, b_ld), shape, _gpu_device(op, dev, dev_b)
+
+
+def _grad_operand(op, grad, of, shape, dev):
+    """(address, pixel stride) of `grad`, a torch tensor of the shape and on the device of the operand named `of`; None for None."""
+    import torch
+    if grad is None:
+        return None
+    if not torch.is_tensor(grad):
+        raise ValueError("%s: grad must be a torch device tensor" % op)
+    pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
+    if shape_g != shape or not _same_device(dev_g, dev):
+        raise ValueError("%s: grad %s on %s does not match %s %s on %s" % (op, shape_g, dev_g, of, shape, dev))
+    return pg, g_ld
+
+
+def _stats_operand(op, stats, count, dev):
+    """The address of `stats`, a dense float32 [count] tensor on `dev`; None for None."""
+    import torch
+    if stats is None:
+        return None
+    if (not torch.is_tensor(stats) or tuple(stats.shape) != (count,) or stats.dtype != torch.float32 or not stats.is_contiguous()
+            or not _same_device(stats.device, dev)):
+        raise ValueError("%s: stats must be a dense float32 [%d] tensor on the flow's device" % (op, count))
+    return stats.data_ptr()
 
 
 _workspaces = {}        # torch device -> uint8 workspace tensor, grown on demand (calls on one stream share it in order)
@@ -218,6 +270,14 @@ def _workspace(device, nbytes):
     return ws
 
 
+def _launch(dev, nbytes, stream):
+    """(a zeroed 0-d result on dev, (address, bytes) of a workspace of nbytes, `stream` or torch's current one of dev)."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    return torch.zeros((), dtype=torch.float32, device=dev), (_workspace(dev, nbytes).data_ptr(), nbytes), stream
+
+
 def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
     """mv3d_image_metrics on device memory.  pred / target: graph Tensors (channel views from split included) or torch device
     tensors, [N,H,W,C] float32.  out: an optional dense float32 [N,3] device tensor to write into.  Asynchronous on `stream`
@@ -225,13 +285,7 @@ def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
     columns (l1, mse, ssim)."""
     import torch
     from . import _lib
-    pa, shape, a_ld, dev = _operand(pred, 'pred')
-    pb, shape_b, b_ld, dev_b = _operand(target, 'target')
-    if shape != shape_b:
-        raise ValueError("image_metrics: pred %s and target %s differ in shape" % (shape, shape_b))
-    dev = torch.device(dev)
-    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
-        raise _lib.Mv3dError("image_metrics runs on the GPU (operands are on %s); image_metrics_host is the numpy form" % dev)
+    a, b, shape, dev = _image_pair('image_metrics', pred, target)
     n, h, w, c = shape
     if out is None:
         out = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -242,7 +296,7 @@ def image_metrics(pred, target, max_val=1.0, out=None, stream=None):
     ws = _workspace(out.device, nbytes)
     if stream is None:
         stream = torch.cuda.current_stream(out.device).cuda_stream
-    lib.image_metrics(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), out.data_ptr(), ws.data_ptr(), nbytes, stream)
+    lib.image_metrics(n, h, w, c, *a, *b, float(max_val), out.data_ptr(), ws.data_ptr(), nbytes, stream)
     return out
 
 
@@ -253,38 +307,13 @@ def ssim_loss(pred, target, max_val=1.0, weight=1.0, grad=None, accumulate=False
     the operand rules of image_metrics.  grad: an optional float32 device tensor of pred's shape with one pixel stride (a
     channel slice of a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream`
     (default: torch's current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
-    import torch
-    from . import _lib
-    pa, shape, a_ld, dev = _operand(pred, 'pred')
-    pb, shape_b, b_ld, dev_b = _operand(target, 'target')
-    if shape != shape_b:
-        raise ValueError("ssim_loss: pred %s and target %s differ in shape" % (shape, shape_b))
-    dev = torch.device(dev)
-    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
-        raise _lib.Mv3dError("ssim_loss runs on the GPU (operands are on %s); ssim_loss_host is the numpy form" % dev)
-    n, h, w, c = shape
-    pg, g_ld = None, c
-    if grad is not None:
-        if not torch.is_tensor(grad):
-            raise ValueError("ssim_loss: grad must be a torch device tensor")
-        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
-        if shape_g != shape or torch.device(dev_g) != dev:
-            raise ValueError("ssim_loss: grad %s on %s does not match pred %s on %s" % (shape_g, dev_g, shape, dev))
-    out = torch.zeros((), dtype=torch.float32, device=dev)
+    from . import _lib, loss_calls
+    a, b, shape, dev = _image_pair('ssim_loss', pred, target)
+    grad = _grad_operand('ssim_loss', grad, 'pred', shape, dev)
+    mask = _mask_operand('ssim_loss', mask, shape, dev)
     lib = _lib.lib()
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    if mask is not None:
-        pm, m_ld = _mask_operand('ssim_loss', mask, shape, dev)
-        nbytes = int(lib.ssim_loss_masked_workspace_bytes(n, h, w, c))
-        ws = _workspace(dev, nbytes)
-        lib.ssim_loss_masked(n, h, w, c, pa, a_ld, pb, b_ld, pm, m_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld,
-                             1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
-        return out
-    nbytes = int(lib.ssim_loss_workspace_bytes(n, h, w, c))
-    ws = _workspace(dev, nbytes)
-    lib.ssim_loss(n, h, w, c, pa, a_ld, pb, b_ld, float(max_val), float(weight), out.data_ptr(), pg, g_ld, 1 if accumulate else 0,
-                  ws.data_ptr(), nbytes, stream)
+    out, ws, stream = _launch(dev, loss_calls.ssim_workspace_bytes(lib, shape, mask is not None), stream)
+    loss_calls.ssim(lib, shape, a, b, mask, max_val, weight, out.data_ptr(), grad, accumulate, ws, stream)
     return out
 
 
@@ -367,51 +396,28 @@ def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.f
     return loss, grad
 
 
-def _same_device(a, b):
-    """A graph Tensor names its device as the graph was given it ('cuda'), a torch tensor with its index ('cuda:0')."""
-    import torch
-    a, b = torch.device(a), torch.device(b)
-    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
-
-
 def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, grad=None, accumulate=False, stream=None):
     """mv3d_flow_smoothness on device memory: weight * S of flow_smoothness_host, and optionally its gradient with respect to the
     flow.  flow / guide: graph Tensors (channel views included) or torch device tensors, float32 [N,H,W,2] / [N,H,W,1..4].  grad: an
     optional float32 device tensor of the flow's shape with one pixel stride (a channel slice of a dense tensor works); it is
     overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's current stream of the operands'
     device).  Returns the loss as a 0-d device tensor."""
-    import torch
-    from . import _lib
+    from . import _lib, loss_calls
     pf, shape, f_ld, dev = _operand(flow, 'flow')
     _smooth_shape(shape)
     edge_alpha, eps, weight = _smooth_scalars(edge_alpha, eps, weight)      # the twin's checks: the same ValueError for the same argument
-    dev = torch.device(dev)
-    pgd, g_c, gd_ld = None, 0, 0
     if guide is not None:
         pgd, shape_g, gd_ld, dev_g = _operand(guide, 'guide')
         if shape_g[:3] != shape[:3] or not 1 <= shape_g[3] <= 4:
             raise ValueError("flow_smoothness: guide must be [N,H,W,1..4] over the flow's %s, got shape %s" % (shape[:3], shape_g))
         if not _same_device(dev_g, dev):
             raise ValueError("flow_smoothness: guide on %s, flow on %s" % (dev_g, dev))
-        g_c = shape_g[3]
-    if dev.type != 'cuda':
-        raise _lib.Mv3dError("flow_smoothness runs on the GPU (operands are on %s); flow_smoothness_host is the numpy form" % dev)
-    n, h, w, _ = shape
-    pg, g_ld = None, 2
-    if grad is not None:
-        if not torch.is_tensor(grad):
-            raise ValueError("flow_smoothness: grad must be a torch device tensor")
-        pg, shape_gr, g_ld, dev_gr = _operand(grad, 'grad')
-        if shape_gr != shape or not _same_device(dev_gr, dev):
-            raise ValueError("flow_smoothness: grad %s on %s does not match flow %s on %s" % (shape_gr, dev_gr, shape, dev))
-    out = torch.zeros((), dtype=torch.float32, device=dev)
+        guide = (pgd, shape_g[3], gd_ld)
+    dev = _gpu_device('flow_smoothness', dev)
+    grad = _grad_operand('flow_smoothness', grad, 'flow', shape, dev)
     lib = _lib.lib()
-    nbytes = int(lib.flow_smoothness_workspace_bytes(n, h, w))
-    ws = _workspace(dev, nbytes)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    lib.flow_smoothness(n, h, w, pf, f_ld, pgd, g_c, gd_ld, float(edge_alpha), float(eps), float(weight), out.data_ptr(), pg, g_ld,
-                        1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+    out, ws, stream = _launch(dev, loss_calls.flow_smoothness_workspace_bytes(lib, shape[:3]), stream)
+    loss_calls.flow_smoothness(lib, shape[:3], (pf, f_ld), guide, edge_alpha, eps, weight, out.data_ptr(), grad, accumulate, ws, stream)
     return out
 
 
@@ -518,36 +524,16 @@ def flow_consistency(flow, eps=1e-3, weight=1.0, grad=None, accumulate=False, st
     overwritten, or added to when accumulate is true.  stats: an optional dense float32 [2] device tensor that receives the
     unweighted C and the valid fraction.  Asynchronous on `stream` (default: torch's current stream of the operands' device).
     Returns the loss as a 0-d device tensor."""
-    import torch
-    from . import _lib
+    from . import _lib, loss_calls
     pf, shape, f_ld, dev = _operand(flow, 'flow')
     _consist_shape(shape)
     eps, weight = _consist_scalars(eps, weight)              # the twin's checks: the same ValueError for the same argument
-    dev = torch.device(dev)
-    if dev.type != 'cuda':
-        raise _lib.Mv3dError("flow_consistency runs on the GPU (operands are on %s); flow_consistency_host is the numpy form" % dev)
-    n, h, w, _ = shape
-    pg, g_ld = None, 2
-    if grad is not None:
-        if not torch.is_tensor(grad):
-            raise ValueError("flow_consistency: grad must be a torch device tensor")
-        pg, shape_gr, g_ld, dev_gr = _operand(grad, 'grad')
-        if shape_gr != shape or not _same_device(dev_gr, dev):
-            raise ValueError("flow_consistency: grad %s on %s does not match flow %s on %s" % (shape_gr, dev_gr, shape, dev))
-    ps = None
-    if stats is not None:
-        if (not torch.is_tensor(stats) or tuple(stats.shape) != (2,) or stats.dtype != torch.float32 or not stats.is_contiguous()
-                or not _same_device(stats.device, dev)):
-            raise ValueError("flow_consistency: stats must be a dense float32 [2] tensor on the flow's device")
-        ps = stats.data_ptr()
-    out = torch.zeros((), dtype=torch.float32, device=dev)
+    dev = _gpu_device('flow_consistency', dev)
+    grad = _grad_operand('flow_consistency', grad, 'flow', shape, dev)
+    ps = _stats_operand('flow_consistency', stats, 2, dev)
     lib = _lib.lib()
-    nbytes = int(lib.flow_consistency_workspace_bytes(n, h, w))
-    ws = _workspace(dev, nbytes)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    lib.flow_consistency(n, h, w, pf, f_ld, float(eps), float(weight), out.data_ptr(), ps, pg, g_ld, 1 if accumulate else 0,
-                         ws.data_ptr(), nbytes, stream)
+    out, ws, stream = _launch(dev, loss_calls.flow_consistency_workspace_bytes(lib, shape[:3]), stream)
+    loss_calls.flow_consistency(lib, shape[:3], (pf, f_ld), eps, weight, out.data_ptr(), ps, grad, accumulate, ws, stream)
     return out
 
 
@@ -629,9 +615,7 @@ def flow_occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True, out
     pf, shape, f_ld, dev = _operand(flow, 'flow')
     _consist_shape(shape)
     alpha1, alpha2, outside_visible = _occlusion_scalars(alpha1, alpha2, outside_visible)
-    dev = torch.device(dev)
-    if dev.type != 'cuda':
-        raise _lib.Mv3dError("flow_occlusion_mask runs on the GPU (operands are on %s); flow_occlusion_mask_host is the numpy form" % dev)
+    dev = _gpu_device('flow_occlusion_mask', dev)
     n, h, w, _ = shape
     if out is None:
         out = torch.empty((n, h, w, 1), dtype=torch.float32, device=dev)
@@ -641,12 +625,7 @@ def flow_occlusion_mask(flow, alpha1=0.01, alpha2=0.5, outside_visible=True, out
     po, shape_o, o_ld, dev_o = _operand(view, 'out')
     if shape_o != (n, h, w, 1) or not _same_device(dev_o, dev):
         raise ValueError("flow_occlusion_mask: out %s on %s does not match flow %s on %s" % (tuple(out.shape), dev_o, shape, dev))
-    ps = None
-    if stats is not None:
-        if (not torch.is_tensor(stats) or tuple(stats.shape) != (3,) or stats.dtype != torch.float32 or not stats.is_contiguous()
-                or not _same_device(stats.device, dev)):
-            raise ValueError("flow_occlusion_mask: stats must be a dense float32 [3] tensor on the flow's device")
-        ps = stats.data_ptr()
+    ps = _stats_operand('flow_occlusion_mask', stats, 3, dev)
     lib = _lib.lib()
     nbytes = int(lib.flow_occlusion_mask_workspace_bytes(n, h, w)) if ps is not None else 0
     ws = _workspace(dev, nbytes) if nbytes else None
@@ -800,9 +779,8 @@ def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, 
     [N,H,W,1] over the flow's grid on the flow's device (a channel of a wider tensor works): mv3d_multiscale_warp_loss_masked, the
     masked form multiscale_warp_loss_host states.  Returns (value, level_values): a 0-d and a [levels] device tensor.
     Raises ValueError on what the C entry would refuse."""
-    import ctypes
     import torch
-    from . import _lib
+    from . import _lib, loss_calls
     levels, weights, kind = _multiscale_scalars(levels, level_weights, kind)       # the twin's checks: the same ValueError
     pf, shape, f_ld, dev = _operand(flow, 'flow')
     ps, shape_s, s_ld, dev_s = _operand(src, 'src')
@@ -810,35 +788,15 @@ def multiscale_warp_loss(src, flow, target, levels, level_weights=None, kind=2, 
     _multiscale_shapes(shape_s, shape, shape_t, levels)
     if not _same_device(dev_s, dev) or not _same_device(dev_t, dev):
         raise ValueError("multiscale_warp_loss: src on %s, target on %s, flow on %s" % (dev_s, dev_t, dev))
-    pm, m_ld = None, 1
-    if mask is not None:
-        pm, m_ld = _mask_operand('multiscale_warp_loss', mask, shape, dev)
-    dev = torch.device(dev)
-    if dev.type != 'cuda':
-        raise _lib.Mv3dError("multiscale_warp_loss runs on the GPU (operands are on %s); multiscale_warp_loss_host is the numpy form" % dev)
-    n, h, w, _ = shape
-    pg, g_ld = None, 2
-    if grad is not None:
-        if not torch.is_tensor(grad):
-            raise ValueError("multiscale_warp_loss: grad must be a torch device tensor")
-        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
-        if shape_g != shape or not _same_device(dev_g, dev):
-            raise ValueError("multiscale_warp_loss: grad %s on %s does not match flow %s on %s" % (shape_g, dev_g, shape, dev))
-    out = torch.zeros((), dtype=torch.float32, device=dev)
+    mask = _mask_operand('multiscale_warp_loss', mask, shape, dev)
+    dev = _gpu_device('multiscale_warp_loss', dev)
+    grad = _grad_operand('multiscale_warp_loss', grad, 'flow', shape, dev)
     level_values = torch.zeros((levels,), dtype=torch.float32, device=dev)
     lib = _lib.lib()
-    nbytes = int(lib.multiscale_warp_loss_workspace_bytes(n, h, w, shape_s[1], shape_s[2], shape_t[3], levels))
-    ws = _workspace(dev, nbytes)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    if mask is not None:
-        lib.multiscale_warp_loss_masked(n, h, w, shape_s[1], shape_s[2], shape_t[3], ps, s_ld, pf, f_ld, pt, t_ld, pm, m_ld, levels,
-                                        (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
-                                        1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)
-        return out, level_values
-    lib.multiscale_warp_loss(n, h, w, shape_s[1], shape_s[2], shape_t[3], ps, s_ld, pf, f_ld, pt, t_ld, levels,
-                             (ctypes.c_float * levels)(*weights), kind, out.data_ptr(), level_values.data_ptr(), pg, g_ld,
-                             1 if accumulate else 0, 0, ws.data_ptr(), nbytes, stream)
+    src_hwc = (shape_s[1], shape_s[2], shape_t[3])
+    out, ws, stream = _launch(dev, loss_calls.multiscale_workspace_bytes(lib, shape[:3], src_hwc, levels), stream)
+    loss_calls.multiscale(lib, shape[:3], src_hwc, (ps, s_ld), (pf, f_ld), (pt, t_ld), mask, levels, weights, kind, out.data_ptr(),
+                          level_values.data_ptr(), grad, accumulate, False, ws, stream)
     return out, level_values
 
 
@@ -974,34 +932,11 @@ def census_loss(a, b, max_val=1.0, weight=1.0, radius=3, eps=0.01, grad=None, ac
     operand rules of image_metrics.  grad: an optional float32 device tensor of a's shape with one pixel stride (a channel slice of
     a dense tensor works); it is overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's
     current stream of the operands' device).  Returns the loss as a 0-d device tensor."""
-    import torch
-    from . import _lib
-    pa, shape, a_ld, dev = _operand(a, 'pred')
-    pb, shape_b, b_ld, dev_b = _operand(b, 'target')
-    if shape != shape_b:
-        raise ValueError("census_loss: pred %s and target %s differ in shape" % (shape, shape_b))
-    dev = torch.device(dev)
-    if dev.type != 'cuda' or torch.device(dev_b).type != 'cuda':
-        raise _lib.Mv3dError("census_loss runs on the GPU (operands are on %s); census_loss_host is the numpy form" % dev)
-    n, h, w, c = shape
-    pg, g_ld = None, c
-    if grad is not None:
-        if not torch.is_tensor(grad):
-            raise ValueError("census_loss: grad must be a torch device tensor")
-        pg, shape_g, g_ld, dev_g = _operand(grad, 'grad')
-        if shape_g != shape or torch.device(dev_g) != dev:
-            raise ValueError("census_loss: grad %s on %s does not match pred %s on %s" % (shape_g, dev_g, shape, dev))
-    out = torch.zeros((), dtype=torch.float32, device=dev)
+    from . import _lib, loss_calls
+    pa, pb, shape, dev = _image_pair('census_loss', a, b)
+    grad = _grad_operand('census_loss', grad, 'pred', shape, dev)
+    mask = _mask_operand('census_loss', mask, shape, dev)
     lib = _lib.lib()
-    nbytes = int(lib.census_loss_workspace_bytes(n, h, w, c, int(radius)))
-    ws = _workspace(dev, nbytes)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    if mask is not None:
-        pm, m_ld = _mask_operand('census_loss', mask, shape, dev)
-        lib.census_loss_masked(n, h, w, c, pa, a_ld, pb, b_ld, pm, m_ld, int(radius), float(max_val), float(eps), float(weight),
-                               out.data_ptr(), pg, g_ld, 1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
-        return out
-    lib.census_loss(n, h, w, c, pa, a_ld, pb, b_ld, int(radius), float(max_val), float(eps), float(weight), out.data_ptr(), pg, g_ld,
-                    1 if accumulate else 0, ws.data_ptr(), nbytes, stream)
+    out, ws, stream = _launch(dev, loss_calls.census_workspace_bytes(lib, shape, radius), stream)
+    loss_calls.census(lib, shape, pa, pb, mask, radius, max_val, eps, weight, out.data_ptr(), grad, accumulate, ws, stream)
     return out

@@ -678,19 +678,18 @@ class ModelBase(object):
             return (1, into(lambda loss: metrics.flow_smoothness(flow, guide, alpha, eps)),
                     lambda loss: float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None, alpha, eps)[0]),
                     means(name + '/smoothness'))
-        def multiscale(name, flow, src, target, levels, kind):
-            return (levels, into(lambda loss: metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind])[1]),
-                    lambda loss: metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None, ms_kind[kind])[2],
-                    means(*['%s/photo_x%d' % (name, 2 << l) for l in range(levels)]))
-        def masked_multiscale(name, flow, src, target, levels, kind, mask):     # the masked level terms as trained
+        def host_mask(mask):
+            return mask.numpy() if mask is not None else None
+        def multiscale(name, flow, src, target, levels, kind, mask=None, suffix=''):     # suffix '_masked': the masked level terms as trained
             return (levels, into(lambda loss: metrics.multiscale_warp_loss(src, flow, target, levels, None, ms_kind[kind], mask=mask)[1]),
                     lambda loss: metrics.multiscale_warp_loss_host(src.numpy(), flow.numpy(), target.numpy(), levels, None, ms_kind[kind],
-                                                                   mask=mask.numpy())[2],
-                    means(*['%s/photo_x%d_masked' % (name, 2 << l) for l in range(levels)]))
-        def census(name, pred, target, max_val, radius, eps):
-            return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps)),
-                    lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps)[0]),
-                    means(name + '/census'))
+                                                                   mask=host_mask(mask))[2],
+                    means(*['%s/photo_x%d%s' % (name, 2 << l, suffix) for l in range(levels)]))
+        def census(name, pred, target, max_val, radius, eps, mask=None, suffix=''):
+            return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps, mask=mask)),
+                    lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps,
+                                                                mask=host_mask(mask))[0]),
+                    means(name + '/census' + suffix))
         def consistency(name, flow, eps):
             return (2, lambda out, loss: metrics.flow_consistency(flow, eps, 1.0, stats=out),
                     lambda loss: [float(v) for v in metrics.flow_consistency_host(flow.numpy(), eps)[2:]],
@@ -701,13 +700,12 @@ class ModelBase(object):
                     means(*['%s/%s' % (name, what) for what in ('visible', 'occluded', 'outside')]))
         def masked_image(name, what, pred, target, mask, max_val, radius, eps):       # the masked SSIM / census term as trained
             if what == 'census_masked':
-                return (1, into(lambda loss: metrics.census_loss(pred, target, max_val, 1.0, radius, eps, mask=mask)),
-                        lambda loss: float(metrics.census_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, radius, eps,
-                                                                    mask=mask.numpy())[0]),
-                        means(name + '/census_masked'))
+                return census(name, pred, target, max_val, radius, eps, mask, '_masked')
             return (1, into(lambda loss: metrics.ssim_loss(pred, target, max_val, 1.0, mask=mask)),
                     lambda loss: float(metrics.ssim_loss_host(pred.numpy(), target.numpy(), max_val, np.float64, 1.0, mask=mask.numpy())[0]),
                     means(name + '/ssim_loss_masked'))
+        def masked_multiscale(*term):   # a multiscale_terms tuple with the mask behind it
+            return multiscale(*term, suffix='_masked')
         report = [(1, into(lambda loss: loss), float, means('loss'))] if self.graph.loss_expr is not None else []
         report += [pair(*p) for p in pairs]
         for make, attr in ((smoothness, 'smoothness_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
