@@ -76,6 +76,7 @@ STATUS_FUNCS = {
     "mv3d_ssim_loss_masked": [_i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_census_loss_masked": [_i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_smoothness": [_i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
+    "mv3d_flow_smoothness2": [_i, _i, _i, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_consistency": [_i, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp],
     "mv3d_flow_occlusion_mask": [_i, _i, _i, _vp, _i, _f, _f, _i, _vp, _i, _vp, _vp, _sz, _vp],
     "mv3d_warp_resample_occlusion_loss": [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _i, _vp, _i,
@@ -152,6 +153,7 @@ OTHER_FUNCS = {
     "mv3d_census_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mv3d_ssim_loss_masked_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mv3d_flow_smoothness_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mv3d_flow_smoothness2_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_flow_consistency_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_flow_occlusion_mask_workspace_bytes": (_sz, [_i, _i, _i]),
     "mv3d_warp_resample_occlusion_loss_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -394,22 +394,25 @@ class CensusTerm(LossTerm):
 
 class SmoothTerm(LossTerm):
     """The edge-aware smoothness of the flow a (mv3d_flow_smoothness) with b the guide image or None, edge parameter edge_alpha
-    and Charbonnier eps.  The workspace holds 2 sums per tile."""
+    and Charbonnier eps; with second_order the penalty of the second differences (mv3d_flow_smoothness2), which takes the same
+    operands (`order` is the launch position, hence the keyword's name).  The workspace holds 2 sums per tile."""
     kind, order, on_flow = LOSS_SMOOTH, 3, True
 
-    def __init__(self, a, b, edge_alpha=0.0, eps=1e-3):
+    def __init__(self, a, b, edge_alpha=0.0, eps=1e-3, second_order=False):
         LossTerm.__init__(self, a, b)
-        self.edge_alpha, self.eps = float(edge_alpha), float(eps)
+        self.edge_alpha, self.eps, self.second_order = float(edge_alpha), float(eps), bool(second_order)
 
     def workspace_bytes(self, lib):
-        return self._nonzero(loss_calls.flow_smoothness_workspace_bytes(lib, self.a.shape[:3]),
-                             "flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness takes" % (self.a.shape,))
+        difference = 2 if self.second_order else 1
+        return self._nonzero(loss_calls.flow_smoothness_workspace_bytes(lib, self.a.shape[:3], difference),
+                             "flow_smoothness_loss: a flow of shape %s is outside what mv3d_flow_smoothness%s takes"
+                             % (self.a.shape, '2' if self.second_order else ''))
 
     def launch(self, g, w, value, grad, accumulate):
         b = self.b
         loss_calls.flow_smoothness(g.lib, self.a.shape[:3], _at(self.a), (b.ptr, b.C, b.ld) if b is not None else None, self.edge_alpha,
                                    self.eps, w, g.loss_buf.data_ptr() if value else None, self._grad_at(grad), grad and accumulate,
-                                   self._ws_at(), g.stream)
+                                   self._ws_at(), g.stream, 2 if self.second_order else 1)
 
 
 class MultiscaleTerm(LossTerm):

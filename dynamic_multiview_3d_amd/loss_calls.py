@@ -1,6 +1,6 @@
 """The library calls of the loss kernels that have a recorded caller (the LossTerm classes of graph.py) and an eager one (the
 wrappers of metrics.py): one function per family, the only place that lays out the positional arguments of its entry
-(include/mv3d_hip.h) and that chooses between an entry and its masked form.
+(include/mv3d_hip.h) and that chooses between an entry and its masked form (for the flow smoothness: between the first- and the second-order entry).
 
 Operands arrive resolved.  `lib` is _lib.lib().  An operand is its (address, pixel stride) pair, or None where it is optional and
 absent: `mask` (None = the unmasked entry; a pair is spliced into the same argument list, behind the operands, for the masked entry),
@@ -35,14 +35,15 @@ def census(lib, shape, a, b, mask, radius, max_val, eps, weight, loss, grad, acc
     return lib.census_loss(*head, *tail) if mask is None else lib.census_loss_masked(*head, *mask, *tail)
 
 
-def flow_smoothness_workspace_bytes(lib, nhw):
-    return int(lib.flow_smoothness_workspace_bytes(*nhw))
+def flow_smoothness_workspace_bytes(lib, nhw, order=1):
+    return int((lib.flow_smoothness2_workspace_bytes if order == 2 else lib.flow_smoothness_workspace_bytes)(*nhw))
 
 
-def flow_smoothness(lib, nhw, flow, guide, edge_alpha, eps, weight, loss, grad, accumulate, ws, stream):
-    """mv3d_flow_smoothness of a flow over (N, H, W)."""
-    lib.flow_smoothness(*nhw, *flow, *(guide if guide is not None else (None, 0, 0)), float(edge_alpha), float(eps), float(weight),
-                        loss, *_grad(grad, 2), 1 if accumulate else 0, *ws, stream)
+def flow_smoothness(lib, nhw, flow, guide, edge_alpha, eps, weight, loss, grad, accumulate, ws, stream, order=1):
+    """mv3d_flow_smoothness (order 1) / mv3d_flow_smoothness2 (order 2) of a flow over (N, H, W): one argument list."""
+    entry = lib.flow_smoothness2 if order == 2 else lib.flow_smoothness
+    entry(*nhw, *flow, *(guide if guide is not None else (None, 0, 0)), float(edge_alpha), float(eps), float(weight),
+          loss, *_grad(grad, 2), 1 if accumulate else 0, *ws, stream)
 
 
 def multiscale_workspace_bytes(lib, nhw, src_hwc, levels):

@@ -330,18 +330,25 @@ def _smooth_scalars(edge_alpha, eps, weight):
     return edge_alpha, eps, weight
 
 
-def _smooth_shape(shape):
+def _smooth_order(order):
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order not in (1, 2):
+        raise ValueError("flow_smoothness: order must be 1 or 2, got %r" % (order,))
+    return int(order)
+
+
+def _smooth_shape(shape, order=1):
     if len(shape) != 4 or shape[3] != 2:
         raise ValueError("flow_smoothness: flow must be [N,H,W,2], got %s" % (tuple(shape),))
-    if shape[0] < 1 or shape[1] < 2 or shape[2] < 2:
-        raise ValueError("flow_smoothness: flow %s needs N >= 1 and H, W >= 2" % (tuple(shape),))
+    side = order + 1                                         # a difference of this order spans order + 1 pixels
+    if shape[0] < 1 or shape[1] < side or shape[2] < side:
+        raise ValueError("flow_smoothness: flow %s needs N >= 1 and H, W >= %d" % (tuple(shape), side))
 
 
-def _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype):
+def _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype, order=1):
     """The operand checks of the flow-smoothness functions: (flow, guide or None) in `dtype`, and edge_alpha, eps, weight as the
     floats the C ABI takes."""
     f = np.asarray(flow).astype(dtype)
-    _smooth_shape(f.shape)
+    _smooth_shape(f.shape, order)
     g = None
     if guide is not None:
         g = np.asarray(guide).astype(dtype)
@@ -351,7 +358,7 @@ def _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype):
     return f, g, edge_alpha, eps, weight
 
 
-def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.float64, weight=1.0):
+def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.float64, weight=1.0, order=1):
     """(loss, grad) of the edge-aware first-order smoothness of a flow [N,H,W,2]: loss = weight * S, a scalar of `dtype`, and
     grad = d loss / d flow, [N,H,W,2] in `dtype`; every step in `dtype` arithmetic.  At float32 this states mv3d_flow_smoothness's
     own operation order (csrc/flow_smooth.hip); only the two sums behind S (the kernel keeps them in double) and exp differ.
@@ -361,9 +368,14 @@ def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.f
       r = sqrt(d * d + eps * eps)          phi = r - eps (Charbonnier)          phi' = d / r
       S = sum(wx * phi(dx)) / Zx + sum(wy * phi(dy)) / Zy,      Zx = N H (W-1) 2,  Zy = N (H-1) W 2
       grad[i, j] = (ex[i, j-1] - ex[i, j]) * (weight / Zx) + (ey[i-1, j] - ey[i, j]) * (weight / Zy),   e = w * phi', 0 out of range
-    The guide is not differentiated.  sqrt(eps * eps) == eps, so a constant flow gives exactly (0, zeros)."""
+    The guide is not differentiated.  sqrt(eps * eps) == eps, so a constant flow gives exactly (0, zeros).
+
+    order=2 is the second-order term, the twin of mv3d_flow_smoothness2 (H, W >= 3): _smooth2_host states it."""
     dtype = np.dtype(dtype).type
-    f, g, edge_alpha, eps, weight = _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype)
+    order = _smooth_order(order)
+    f, g, edge_alpha, eps, weight = _smooth_operands(flow, guide, edge_alpha, eps, weight, dtype, order)
+    if order == 2:
+        return _smooth2_host(f, g, edge_alpha, eps, weight, dtype)
     n, h, w, _ = f.shape
     eps_t = dtype(eps)
     eps2 = eps_t * eps_t
@@ -396,15 +408,76 @@ def flow_smoothness_host(flow, guide=None, edge_alpha=10.0, eps=1e-3, dtype=np.f
     return loss, grad
 
 
-def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, grad=None, accumulate=False, stream=None):
-    """mv3d_flow_smoothness on device memory: weight * S of flow_smoothness_host, and optionally its gradient with respect to the
-    flow.  flow / guide: graph Tensors (channel views included) or torch device tensors, float32 [N,H,W,2] / [N,H,W,1..4].  grad: an
+def _smooth2_slices(axis):
+    """The index tuples of the -, c and + pixels of every three-pixel stencil along `axis` of an [N,H,W,C] array."""
+    lo, mid, hi = ([slice(None)] * 4 for _ in range(3))
+    lo[axis], mid[axis], hi[axis] = slice(None, -2), slice(1, -1), slice(2, None)
+    return tuple(lo), tuple(mid), tuple(hi)
+
+
+def _smooth2_weights(g, edge_alpha, axis, dtype):
+    """The stencil weights of _smooth2_host along `axis` for the guide g (in `dtype`), one per stencil centre."""
+    lo, mid, hi = _smooth2_slices(axis)
+    below, above = np.abs(g[mid] - g[lo]), np.abs(g[hi] - g[mid])
+    s = np.zeros(below.shape[:3], dtype)
+    for k in range(below.shape[3]):                          # channels in index order, the lower edge before the upper one
+        s = s + below[..., k]
+        s = s + above[..., k]
+    return np.exp(-(dtype(edge_alpha / g.shape[3]) * s)).astype(dtype)
+
+
+def _smooth2_host(f, g, edge_alpha, eps, weight, dtype):
+    """flow_smoothness_host at order 2 on checked operands: the penalty of the second differences, which is minimal for an affine
+    flow.  Along an axis, with c the centre of a three-pixel stencil and -, + its neighbours (x centres j = 1..W-2, y centres
+    i = 1..H-2):
+
+      d = (f[+] - f[c]) - (f[c] - f[-])                           per flow channel
+      s = 0;  for k: s = s + |I[c,k] - I[-,k]|;  s = s + |I[+,k] - I[c,k]|
+      w = exp(-((edge_alpha / Cg) * s))                            1 without a guide or with edge_alpha == 0 (no guide is read):
+                                                                   the product of the first-order weights of the two edges spanned
+      r = sqrt(d * d + eps * eps)      v = w * (r - eps)           e = w * (d / r)
+      S2 = sum(vx) / Z2x + sum(vy) / Z2y,      Z2x = N H (W-2) 2,  Z2y = N (H-2) W 2
+      grad[i, j] = ((ex[i, j-1] - ex[i, j]) - (ex[i, j] - ex[i, j+1])) * (weight / Z2x)
+                 + ((ey[i-1, j] - ey[i, j]) - (ey[i, j] - ey[i+1, j])) * (weight / Z2y),      e = 0 where no stencil is centred
+    A flow whose first differences are exact and equal along each axis (constant, affine with dyadic coefficients) gives exactly
+    (0, zeros) under any guide."""
+    n, h, w, _ = f.shape
+    eps_t = dtype(eps)
+    eps2 = eps_t * eps_t
+    zx, zy = float(n) * h * (w - 2) * 2.0, float(n) * (h - 2) * w * 2.0
+
+    def stencils(axis):
+        lo, mid, hi = _smooth2_slices(axis)
+        d = (f[hi] - f[mid]) - (f[mid] - f[lo])
+        if g is None or edge_alpha == 0:
+            wgt = np.ones(d.shape[:3] + (1,), dtype)
+        else:
+            wgt = _smooth2_weights(g, edge_alpha, axis, dtype)[..., None]
+        r = np.sqrt(d * d + eps2)
+        return wgt * (d / r), wgt * (r - eps_t)
+
+    ex, vx = stencils(2)
+    ey, vy = stencils(1)
+    loss = dtype(weight * (float(vx.sum(dtype=dtype)) / zx + float(vy.sum(dtype=dtype)) / zy))
+    px = np.zeros((n, h, w + 2, 2), dtype)                   # ex at centre j sits at column j + 1
+    px[:, :, 2:w] = ex
+    py = np.zeros((n, h + 2, w, 2), dtype)
+    py[:, 2:h] = ey
+    grad = (((px[:, :, :-2] - px[:, :, 1:-1]) - (px[:, :, 1:-1] - px[:, :, 2:])) * dtype(weight / zx)
+            + ((py[:, :-2] - py[:, 1:-1]) - (py[:, 1:-1] - py[:, 2:])) * dtype(weight / zy))
+    return loss, grad
+
+
+def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, grad=None, accumulate=False, stream=None, order=1):
+    """mv3d_flow_smoothness on device memory (order=2: mv3d_flow_smoothness2, H, W >= 3): weight * S of flow_smoothness_host at that
+    order, and optionally its gradient with respect to the flow.  flow / guide: graph Tensors (channel views included) or torch device tensors, float32 [N,H,W,2] / [N,H,W,1..4].  grad: an
     optional float32 device tensor of the flow's shape with one pixel stride (a channel slice of a dense tensor works); it is
     overwritten, or added to when accumulate is true.  Asynchronous on `stream` (default: torch's current stream of the operands'
     device).  Returns the loss as a 0-d device tensor."""
     from . import _lib, loss_calls
     pf, shape, f_ld, dev = _operand(flow, 'flow')
-    _smooth_shape(shape)
+    order = _smooth_order(order)
+    _smooth_shape(shape, order)
     edge_alpha, eps, weight = _smooth_scalars(edge_alpha, eps, weight)      # the twin's checks: the same ValueError for the same argument
     if guide is not None:
         pgd, shape_g, gd_ld, dev_g = _operand(guide, 'guide')
@@ -416,8 +489,9 @@ def flow_smoothness(flow, guide=None, edge_alpha=10.0, eps=1e-3, weight=1.0, gra
     dev = _gpu_device('flow_smoothness', dev)
     grad = _grad_operand('flow_smoothness', grad, 'flow', shape, dev)
     lib = _lib.lib()
-    out, ws, stream = _launch(dev, loss_calls.flow_smoothness_workspace_bytes(lib, shape[:3]), stream)
-    loss_calls.flow_smoothness(lib, shape[:3], (pf, f_ld), guide, edge_alpha, eps, weight, out.data_ptr(), grad, accumulate, ws, stream)
+    out, ws, stream = _launch(dev, loss_calls.flow_smoothness_workspace_bytes(lib, shape[:3], order), stream)
+    loss_calls.flow_smoothness(lib, shape[:3], (pf, f_ld), guide, edge_alpha, eps, weight, out.data_ptr(), grad, accumulate, ws, stream,
+                               order)
     return out
 
 

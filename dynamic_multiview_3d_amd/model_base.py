@@ -204,6 +204,19 @@ def flow_smoothness_from_conf(conf):
     return w, alpha, eps
 
 
+def flow_smoothness_order_from_conf(conf):
+    """1 or 2: conf['flow_smoothness_order'], the order of the differences conf['flow_smoothness_weight'] penalises.  1 (absent,
+    None or 1): first differences, minimal for a constant flow, exactly as without the key.  2: second differences
+    (mv3d_flow_smoothness2), minimal for an affine flow, with the same edge and eps keys.  Raises ValueError on a bool, a
+    non-integer or any other value, whether or not the weight is set, before any device work."""
+    order = conf.get('flow_smoothness_order')
+    if order is None:
+        return 1
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order not in (1, 2):
+        raise ValueError("conf['flow_smoothness_order'] must be 1 or 2, got %r" % (order,))
+    return int(order)
+
+
 def flow_consistency_from_conf(conf):
     """(weight, eps) of the forward-backward consistency switch: conf['flow_consistency_weight'] (0.0 when absent, None or 0, which
     leaves the loss and the recorded plans as they are) and conf['flow_consistency_eps'] (the Charbonnier epsilon in pixels,
@@ -373,6 +386,7 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['census_loss_weight']" % type(self).__name__)
         if flow_smoothness_from_conf(self.conf)[0] > 0 and not self.supports_flow_smoothness:
             raise ValueError("%s does not support conf['flow_smoothness_weight']" % type(self).__name__)
+        flow_smoothness_order_from_conf(self.conf)          # a bad order is refused whether or not the weight is set
         if multiscale_loss_from_conf(self.conf)[0] > 0 and not self.supports_multiscale_loss:
             raise ValueError("%s has no flow: it does not support conf['multiscale_loss_levels']" % type(self).__name__)
         from .pair_swap import pair_swap_from_conf
@@ -478,15 +492,19 @@ class ModelBase(object):
         """conf['flow_smoothness_weight'] * flow_smoothness_loss(flow, guide, edge, eps) on one flow head, or 0 when the switch is
         absent or 0 (the graph then records exactly what it recorded without the key).  The guide (the target view's colour
         image: the flow is indexed by output pixel) is dropped when conf['flow_smoothness_edge'] is 0 or None.  evaluate()
-        reports the unweighted term as '<name>/smoothness'."""
+        reports the unweighted term as '<name>/smoothness'.  With conf['flow_smoothness_order'] = 2 the term is the second-order
+        one (flow_smoothness_loss(..., order=2)) and evaluate() reports it as '<name>/smoothness2' and no '<name>/smoothness': the
+        two figures are not comparable."""
         from .tf_utils import flow_smoothness_loss
         w, alpha, eps = flow_smoothness_from_conf(self.conf)
+        order = flow_smoothness_order_from_conf(self.conf)
         if w == 0:
             return 0
         if alpha == 0:
             guide = None
-        self._note_term('smoothness_terms', (name, flow, guide, alpha, eps))       # (name, flow, guide or None, edge_alpha, eps)
-        return flow_smoothness_loss(flow, guide, alpha, eps) * w
+        # (name, flow, guide or None, edge_alpha, eps)
+        self._note_term('smoothness2_terms' if order == 2 else 'smoothness_terms', (name, flow, guide, alpha, eps))
+        return flow_smoothness_loss(flow, guide, alpha, eps, order) * w
 
     def _eval_pair(self, op, pred, target):
         """(name, max_val) of this model's eval_pairs() entry for the pair."""
@@ -674,10 +692,13 @@ class ModelBase(object):
                         (name + '/ssim', float(s[:, metrics.SSIM].mean()))]
             return (3 * n, lambda out, loss: metrics.image_metrics(pred, target, max_val, out=out.view(n, 3)),
                     lambda loss: metrics.image_metrics_host(pred.numpy(), target.numpy(), max_val).reshape(-1), result)
-        def smoothness(name, flow, guide, alpha, eps):
-            return (1, into(lambda loss: metrics.flow_smoothness(flow, guide, alpha, eps)),
-                    lambda loss: float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None, alpha, eps)[0]),
-                    means(name + '/smoothness'))
+        def smoothness(name, flow, guide, alpha, eps, order=1):
+            return (1, into(lambda loss: metrics.flow_smoothness(flow, guide, alpha, eps, order=order)),
+                    lambda loss: float(metrics.flow_smoothness_host(flow.numpy(), guide.numpy() if guide is not None else None, alpha, eps,
+                                                                    order=order)[0]),
+                    means(name + ('/smoothness2' if order == 2 else '/smoothness')))
+        def smoothness2(*term):         # a smoothness2_terms tuple: the second-order term under its own key
+            return smoothness(*term, order=2)
         def host_mask(mask):
             return mask.numpy() if mask is not None else None
         def multiscale(name, flow, src, target, levels, kind, mask=None, suffix=''):     # suffix '_masked': the masked level terms as trained
@@ -708,7 +729,7 @@ class ModelBase(object):
             return multiscale(*term, suffix='_masked')
         report = [(1, into(lambda loss: loss), float, means('loss'))] if self.graph.loss_expr is not None else []
         report += [pair(*p) for p in pairs]
-        for make, attr in ((smoothness, 'smoothness_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
+        for make, attr in ((smoothness, 'smoothness_terms'), (smoothness2, 'smoothness2_terms'), (multiscale, 'multiscale_terms'), (census, 'census_terms'),
                            (consistency, 'consistency_terms'), (occlusion, 'occlusion_terms'), (masked_image, 'masked_image_terms'),
                            (masked_multiscale, 'masked_multiscale_terms')):
             report += [make(*term) for term in getattr(self, attr, [])]

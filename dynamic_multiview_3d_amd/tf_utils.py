@@ -168,17 +168,21 @@ def census_loss(input1, input2, max_val=1.0, radius=3, eps=0.01, mask=None):
     return ScalarExpr([(1.0, CensusTerm(a, b, max_val, radius, eps, _image_mask('census_loss', mask, a)))])
 
 
-def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
+def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3, order=1):
     """Edge-aware first-order smoothness of a flow field [N,H,W,2] (mv3d_flow_smoothness; metrics.flow_smoothness_host states the
     definition): the mean Charbonnier penalty sqrt(d^2 + eps^2) - eps of the horizontal plus that of the vertical differences,
     each difference weighted by exp(-edge_alpha * mean_k |difference of the guide|) when a guide image [N,H,W,1..4] is given.
     The flow must be differentiated (it is usually an intermediate tensor: its gradient from the consumer and this term's are
-    added); the guide must not be.  Masked and scaled operands are not supported."""
+    added); the guide must not be.  Masked and scaled operands are not supported.  order=2: the same penalty of the SECOND
+    differences (mv3d_flow_smoothness2; H, W >= 3), minimal for an affine flow; a stencil's weight is the product of the weights
+    of the two edges it spans."""
+    from .metrics import _smooth_order
     if isinstance(guide, (_Masked, _Scaled)):
         raise NotImplementedError("flow_smoothness_loss of a masked or scaled operand")
     _check_flow('flow_smoothness_loss', flow)
-    if flow.shape[1] < 2 or flow.shape[2] < 2:
-        raise ValueError("flow_smoothness_loss: needs H, W >= 2, got %s" % (flow.shape,))
+    order = _smooth_order(order)
+    if flow.shape[1] < order + 1 or flow.shape[2] < order + 1:
+        raise ValueError("flow_smoothness_loss: needs H, W >= %d, got %s" % (order + 1, flow.shape,))
     if not flow.requires_grad:
         raise ValueError("flow_smoothness_loss: the flow is not differentiated (nothing to regularise)")
     if guide is not None:
@@ -192,7 +196,7 @@ def flow_smoothness_loss(flow, guide=None, edge_alpha=10.0, eps=1e-3):
         raise ValueError("flow_smoothness_loss: edge_alpha must be finite and >= 0")
     if not (math.isfinite(eps) and eps > 0):
         raise ValueError("flow_smoothness_loss: eps must be finite and positive")
-    return ScalarExpr([(1.0, SmoothTerm(flow, guide, edge_alpha, eps))])
+    return ScalarExpr([(1.0, SmoothTerm(flow, guide, edge_alpha, eps, second_order=order == 2))])
 
 
 def multiscale_photometric_loss(flow, src_img, target, levels=3, level_weights=None, kind='l2', mask=None):

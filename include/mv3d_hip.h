@@ -288,7 +288,7 @@ int mv3d_pixel_loss_strided(int64_t pixels, int ch, const void* a, int a_ld, con
                             const void* mask, int mask_ld, int kind, float weight, void* loss_accum, void* grad, int grad_ld,
                             void* stream);
 int mv3d_fill(void* dst, int64_t count, float value, void* stream);
-/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_multiscale_warp_loss, mv3d_flow_consistency, mv3d_warp_resample_occlusion_loss) stores its term into loss_accum instead of
+/* The NEXT loss call of the calling thread (mv3d_pixel_loss*, mv3d_warp_resample_loss, mv3d_ssim_loss, mv3d_census_loss, mv3d_flow_smoothness, mv3d_flow_smoothness2, mv3d_multiscale_warp_loss, mv3d_flow_consistency, mv3d_warp_resample_occlusion_loss) stores its term into loss_accum instead of
  * adding it: the first term of a recorded step then needs no launch that clears the accumulator (tf.add_n over the terms of
  * appearance_flow_model.py:127-130 starts from the first one). */
 int mv3d_loss_overwrite_next(void);
@@ -451,6 +451,30 @@ size_t mv3d_flow_smoothness_workspace_bytes(int N, int H, int W);
 int mv3d_flow_smoothness(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
                          float edge_alpha, float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- edge-aware SECOND-order flow smoothness: value and gradient with respect to the flow ----------------------------------
+ * The operands, the argument list, the loss word (add by default, store after mv3d_loss_overwrite_next(), a call with loss_accum
+ * NULL leaves the flag pending), grad_accumulate, the channel-slice strides, the workspace rules and the determinism are those of
+ * mv3d_flow_smoothness; H, W >= 3.  Along an axis let c be the centre of a three-pixel stencil and -, + its neighbours (x centres
+ * j = 1..W-2, y centres i = 1..H-2):
+ *   d = (f[+] - f[c]) - (f[c] - f[-])                                     per flow channel
+ *   s = sum_k (|I[c,k] - I[-,k]| + |I[+,k] - I[c,k]|), the two terms of a channel added in this order, channels in index order
+ *   w = exp(-(edge_alpha / guide_c) * s): mathematically the product of mv3d_flow_smoothness's weights of the two edges the
+ *       stencil spans; exactly 1, and no guide read, without a guide or with edge_alpha == 0
+ *   S2 = sum w phi(dx) / (N H (W-2) 2) + sum w phi(dy) / (N (H-2) W 2),   phi, phi' as above
+ *   grad[n,i,j,c] = or += weight * ((ex[i,j-1] - ex[i,j]) - (ex[i,j] - ex[i,j+1])) / Z2x
+ *                          + weight * ((ey[i-1,j] - ey[i,j]) - (ey[i,j] - ey[i+1,j])) / Z2y,   e = w phi'(d), 0 where no stencil is centred
+ * Every step is fp32 without contraction in the order of metrics.py flow_smoothness_host(order=2) at float32; the two sums behind
+ * S2 are kept in double and reduced in a fixed order.  A flow whose first differences are exact and equal along each axis (a
+ * constant flow, an affine flow with dyadic coefficients) gives a value of exactly 0 and a gradient of zeros under any guide.
+ * Plan labels flow_smooth2_tile, flow_smooth2_final (the second only with loss_accum).
+ * mv3d_flow_smoothness2_workspace_bytes() answers 0 for a shape the entry refuses (H or W < 3 among them).
+ * Errors: those of mv3d_flow_smoothness with 3 in place of 2 as the smallest H, W; on any error loss_accum and grad are left
+ * untouched and a pending mv3d_loss_overwrite_next() stays pending. */
+size_t mv3d_flow_smoothness2_workspace_bytes(int N, int H, int W);
+int mv3d_flow_smoothness2(int N, int H, int W, const void* flow, int flow_ld, const void* guide, int guide_c, int guide_ld,
+                          float edge_alpha, float eps, float weight, void* loss_accum, void* grad, int grad_ld, int grad_accumulate,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- multi-scale photometric loss of a flow: value and gradient with respect to the full-resolution flow --------------------
  * src [N,Hs,Ws,C], target [N,H,W,C], flow [N,H,W,2], all fp32 with pixel strides src_ld / target_ld / flow_ld (channel-slice
