@@ -93,6 +93,7 @@ STATUS_FUNCS = {
     "mv3d_u8_to_unit_f32": [_i64, _vp, _vp, _vp],
     "mv3d_u8_process_image": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "mv3d_color_augment": [C.POINTER(_vp), _i, _i, _i, _i, _vp, C.c_uint, _vp, _sz, _vp],
+    "mv3d_geom_augment": [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _i, _i, _vp, _vp, _vp],
     "mv3d_fill": [_vp, _i64, _f, _vp],
     "mv3d_adam_step": [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _vp],
     "mv3d_adam_step_dev": [_i64, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64), _vp],

@@ -18,6 +18,7 @@ class AppearanceFlowModel(ModelBase):
     supports_flow_consistency = True
     supports_pair_swap = True
     supports_occlusion_mask = True
+    supports_geom_augment = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf

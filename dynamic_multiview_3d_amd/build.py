@@ -28,6 +28,7 @@ UNITS = {
     "resampler.hip": ["-ffp-contract=off"],
     "process_image.hip": ["-ffp-contract=off"],
     "color_augment.hip": ["-ffp-contract=off"],
+    "geom_augment.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
     "ssim_loss.hip": ["-ffp-contract=off"],
     "census_loss.hip": ["-ffp-contract=off"],

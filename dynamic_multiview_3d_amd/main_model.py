@@ -13,6 +13,7 @@ from .model_base import ModelBase, optimizer_from_conf
 class Base_Prediction_Model(ModelBase):
     supports_ssim_loss = True
     supports_pair_swap = True       # the five reader tensors of one pair: conf['pair_swap'] is a valid augmentation
+    supports_geom_augment = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf

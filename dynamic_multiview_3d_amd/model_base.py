@@ -377,6 +377,7 @@ class ModelBase(object):
     supports_flow_consistency = False       # the classes whose build_loss() adds flow_consistency_term() set it
     supports_pair_swap = False              # the classes whose inputs are exactly the reader's five tensors (pair_swap.py)
     supports_occlusion_mask = False         # the classes whose build_loss() takes its photometric term from head_loss()
+    supports_geom_augment = False           # the classes whose pose input is the RELATIVE pose disp of a pair (augment.GeomAugment)
 
     def _check_conf(self):
         """Keys that would otherwise be ignored silently; called by a constructor before it builds the graph."""
@@ -401,6 +402,10 @@ class ModelBase(object):
             raise ValueError("%s does not support conf['occlusion_mask_image_terms']" % type(self).__name__)
         if occlusion_multiscale_from_conf(self.conf) and not self.supports_occlusion_mask:
             raise ValueError("%s does not support conf['occlusion_mask_multiscale']" % type(self).__name__)
+        from .augment import geom_from_conf, GEOM_KEYS
+        if geom_from_conf(self.conf).enabled and not self.supports_geom_augment:
+            raise ValueError("%s does not support conf[%s]: its pose input is the absolute pose of a single view, under which no "
+                             "flip, zoom or shift is exact" % (type(self).__name__, ' / '.join(repr(k) for k in GEOM_KEYS)))
 
     def _note_term(self, attr, entry):
         """One more entry of a per-term list that evaluate() reports from (_report); the list exists only once a term was added."""
@@ -553,8 +558,9 @@ class ModelBase(object):
         ema_from_conf(self.conf)        # a bad conf['ema_decay'] raises here, before any device work
         grad_clip_from_conf(self.conf)  # ... and a bad conf['grad_clip_norm']
         grad_accum_from_conf(self.conf)  # ... and a bad conf['grad_accum_steps']
-        from .augment import augment_from_conf
+        from .augment import augment_from_conf, geom_from_conf
         augment_from_conf(self.conf)     # ... and a bad conf['augment_*'] (the input path's colour stage: augment.py)
+        geom_from_conf(self.conf)        # ... and a bad conf['augment_flip' / '_zoom' / '_shift'] (its geometric stage)
         lr_schedule_from_conf(self.conf)  # ... and a bad, stray or misspelt conf['lr_*']
         weight_decay_from_conf(self.conf)  # ... and a bad conf['weight_decay']
         self.graph = Graph(device=device, seed=seed)

@@ -19,6 +19,7 @@ class MultiObjectAppFlow(ModelBase):
     supports_ssim_loss = True
     supports_flow_smoothness = True
     supports_multiscale_loss = True
+    supports_geom_augment = True
 
     def __init__(self, conf, load_tfrec=True, build_loss=True, device=None, seed=1234):
         self.conf = conf

@@ -334,6 +334,9 @@ class TFRecordInput:
     the device mv3d_color_augment in the input thread, on the reader's stream, behind the conversion kernels and before the batch's
     event is recorded; with device='cpu' the numpy twin.  Validation, --evaluate and --visualize inputs never build it, and with
     the keys absent nothing is built and the batches are the plain reader's.
+    With conf['augment_flip' / '_zoom' / '_shift'] (augment.py) the same inputs run the geometric stage behind the colour stage:
+    mv3d_geom_augment on the reader's stream (the numpy twin on the CPU), one transform per record for all of its views, the
+    displacement's azimuth negated under a flip.  Order: conversion / resize, colour, geometry, pair swap.
     With conf['pair_swap'] (pair_swap.py) a batch is made of batch_size / 2 records and their reverses: the files and records
     come in the order they have without the key, consumed half as fast, and the mirror stage runs on the reader's stream behind
     the colour stage (which then draws one map per record), for training, validation, --evaluate and --visualize inputs alike."""
@@ -356,12 +359,14 @@ class TFRecordInput:
         from .pair_swap import pair_swap_from_conf, PairSwap
         self.pair_swap = PairSwap(conf, self.batch) if pair_swap_from_conf(conf) else None
         self.nrec = self.pair_swap.half if self.pair_swap is not None else self.batch        # records per batch
-        self.augment = None
+        self.augment = self.geom = None
         if training and 'test_mode' not in conf:
             from . import augment
+            shapes = {k: (self.nrec,) + tuple(s[1:]) for k, s in input_shapes.items()} if self.pair_swap is not None else input_shapes
             if augment.augment_from_conf(conf).enabled:      # a generator of its own: the shuffle order does not depend on the switch
-                shapes = {k: (self.nrec,) + tuple(s[1:]) for k, s in input_shapes.items()} if self.pair_swap is not None else input_shapes
                 self.augment = augment.ColorAugment(conf, shapes, device=device, rank=rank, ring=self.q.maxsize + 2)
+            if augment.geom_from_conf(conf).enabled:         # one transform per record: both directions of a pair alike
+                self.geom = augment.GeomAugment(conf, shapes, device=device, rank=rank, ring=self.q.maxsize + 2)
         self._stop = False
         self._err = None
         self.thread = threading.Thread(target=self._produce, daemon=True)
@@ -438,6 +443,8 @@ class TFRecordInput:
                             out[k] = d
                         if self.augment is not None:
                             self.augment.apply(out, stream)
+                        if self.geom is not None:
+                            self.geom.apply(out, stream)
                         if self.pair_swap is not None:
                             out = self.pair_swap.apply(out, stream)
                         ev = torch.cuda.Event()
@@ -452,6 +459,8 @@ class TFRecordInput:
                             out[k] = b.clone() if kd else b.to(torch.float32) / np.float32(255.0)
                     if self.augment is not None:
                         self.augment.apply(out)
+                    if self.geom is not None:
+                        self.geom.apply(out)
                     if self.pair_swap is not None:
                         out = self.pair_swap.apply(out)
                 self.q.put((out, ev))

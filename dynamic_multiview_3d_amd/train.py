@@ -30,6 +30,9 @@ With conf['augment_brightness' / '_saturation' / '_hue' / '_contrast'] (augment.
 one colour map per sample over all of its colour views: the TFRecord reader runs it on its own stream, and synthetic training batches
 are handed out as augmented copies (the cycled pool stays pristine).  Validation, --evaluate and --visualize batches are never augmented;
 under data parallelism every rank draws from np.random.default_rng([augment_seed, rank]).
+With conf['augment_flip' / '_zoom' / '_shift'] the training batches then go through the geometric stage (augment.GeomAugment: one flip,
+zoom-in and window shift per sample for all of its views, disp's azimuth negated under a flip), behind the colour stage and in front
+of the pair swap, under the same rules; its generator is np.random.default_rng([augment_seed, rank, 1]).
 With conf['pair_swap'] (pair_swap.py) every batch is conf['batch_size'] / 2 pairs and their reverses, for every input of the graph;
 conf['flow_consistency_weight'] adds the forward-backward consistency term that layout makes possible, and conf['occlusion_mask']
 takes the pixels that term's residual marks as occluded out of the head's photometric loss (`flow_visible` is then logged next to
@@ -288,6 +291,10 @@ def main(argv=None):
             # the pool is cycled: without this the same four batches would repeat forever.  Copies, so that the pool stays pristine
             shapes = {k: tuple(t.shape) for k, t in model.graph.inputs.items()}
             train_data = augment.AugmentedData(train_data, augment.ColorAugment(conf, shapes, device=model.graph.device, rank=rank))
+        if augment.geom_from_conf(conf).enabled and 'test_mode' not in conf:
+            # behind the colour stage (its contrast pivot is a sum in pixel order), in front of the mirror; copies, as above
+            shapes = {k: tuple(t.shape) for k, t in model.graph.inputs.items()}
+            train_data = augment.GeomAugmentedData(train_data, augment.GeomAugment(conf, shapes, device=model.graph.device, rank=rank))
         from . import pair_swap
         if pair_swap.pair_swap_from_conf(conf):
             # the first half of every synthetic batch and its reverses, behind the colour stage: the layout the graph's batch has

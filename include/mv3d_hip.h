@@ -134,6 +134,36 @@ size_t mv3d_color_augment_workspace_bytes(int n, int views, int h, int w);
 int mv3d_color_augment(void* const* images, int views, int n, int h, int w, const void* params, unsigned stages,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- geometric augmentation: flip, centred zoom-in and window shift, ONE transform per sample for all of its views -------------
+ * The three transforms that are exact for a pinhole camera on a turntable (input path: geometric augmentation): a
+ * left-right mirror of every view (the scene reflected in the vertical plane through camera 0's axis: disp = (el1 - el0, az1 - az0)
+ * becomes (el1 - el0, -(az1 - az0))), a longer focal length and a moved principal point (disp unchanged).  No in-plane rotation.
+ * The reference has no augmentation and TensorFlow was never run against this: the contract is the project's own, and
+ * augment.geom_augment_host is its numpy twin and the authority.
+ * src, dst: HOST arrays of `views` (1 .. 16) device pointers, view v float32 [n, h, w, channels[v]] with channels[v] 1 or 3 (a HOST
+ * array, too); read at call time and handed to the kernel by value.  Out of place: no destination equals or overlaps a source or
+ * another destination.  params: device float32 [n, 4] = [m, inv, cxo, cyo] of sample i: m 0 or 1 (flip), inv = 1 / s of the zoom
+ * s >= 1, cxo = cx + ox and cyo = cy + oy with cx = (w - 1) / 2, cy = (h - 1) / 2 and the window offsets ox, oy in source pixels,
+ * each computed in double on the host and rounded once; finite.  disp: device float32 [n, 2], changed in place, or NULL.
+ * Every operation is an fp32 operation that rounds on its own (no contraction).  For output pixel (x, y) of sample i:
+ *   xp = m ? (w - 1) - x : x
+ *   xs = (xp - cx) * inv + cxo;  xs = min(max(xs, 0), w - 1)
+ *   ys = (y  - cy) * inv + cyo;  ys = min(max(ys, 0), h - 1)
+ *   3 channels: x0 = floor(xs), x1 = min(x0 + 1, w - 1), fx = xs - x0; y0, y1, fy likewise; with a, b = src[y0][x0], src[y0][x1] and
+ *               c, d = src[y1][x0], src[y1][x1]: top = a + (b - a) * fx; bot = c + (d - c) * fx; out = top + (bot - top) * fy
+ *               per channel (this lerp returns a for fx = 0 and keeps a constant image constant to the bit)
+ *   1 channel:  nearest: xi = min((int)floor(xs + 0.5f), w - 1), yi likewise; out = src[yi][xi].  Single-channel views are masks and
+ *               depth maps: a mask stays in {0, 1} and depth is never blended across a silhouette.  Under zoom a colour edge and
+ *               its mask edge may therefore differ by up to half a pixel, which is accepted.
+ *   disp[i][1] = m ? -disp[i][1] : disp[i][1]   (disp[i][0] untouched)
+ * The clamp keeps every read in bounds whatever the parameters hold.  One launch per call, no atomics, no workspace, no state;
+ * the grid follows from the work alone and the result does not depend on it.
+ * MV3D_E_INVAL before any launch: src, dst, channels or params NULL, a NULL view; views outside 1 .. 16; a channel count other
+ * than 1 or 3; n, h or w < 1; n*h*w*3 >= 2^31 - 2^21 (32-bit indices); a view, params or a non-NULL disp not 16-byte aligned; any
+ * two of the source and destination buffers equal or overlapping.  Kernel label: geom_augment_kernel. */
+int mv3d_geom_augment(const void* const* src, void* const* dst, const int* channels, int views, int n, int h, int w,
+                      const void* params, void* disp, void* stream);
+
 /* CRC-32C of a host buffer: the record checksum of the reference's TFRecord shards (multi_view_model/utils/read_tf_records.py:46-48
  * reads them through tf.TFRecordReader); used by dynamic_multiview_3d_amd/read_tf_records.py */
 uint32_t mv3d_crc32c(const void* data, size_t n);

@@ -6,7 +6,8 @@ Without --record-size: AppearanceFlowModel, B = 64, 128 x 128 records of the mod
 config 5 -- MultiObjectAppFlow, fully_conv, 256 x 256, B = 32, 13 features -- fed from S x S records that the reader resizes on
 the device (conf['record_image_size'], mv3d_u8_process_image), and additionally the rate of the feeder alone (next() in a loop,
 nothing consuming the batches but a device synchronise at the end), which has to stay above the step's.
---augment sets the four conf['augment_*'] keys (augment.py): the reader then runs the colour stage on its stream on every batch."""
+--augment sets the four conf['augment_*'] keys (augment.py): the reader then runs the colour stage on its stream on every batch.
+--geom sets conf['augment_flip' / '_zoom' / '_shift'] (0.5, 2, 1): the reader then runs the geometric stage behind it."""
 import argparse
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('steps', nargs='?', type=int, default=40)
 ap.add_argument('--record-size', type=int, default=None, help='time config 5 (256 x 256 multi-object) fed from records of this size')
 ap.add_argument('--augment', action='store_true', help='switch on all four colour-augmentation stages of the reader')
+ap.add_argument('--geom', action='store_true', help='switch on flip, zoom and shift: the geometric stage of the reader')
 args = ap.parse_args()
 steps = args.steps
 tmp = tempfile.mkdtemp(prefix='mv3d_feed_')
@@ -44,6 +46,8 @@ else:
         return s
 if args.augment:
     conf.update({'augment_brightness': 0.3, 'augment_saturation': (0.3, 2), 'augment_hue': 0.5, 'augment_contrast': (0.4, 1.8)})
+if args.geom:
+    conf.update({'augment_flip': 0.5, 'augment_zoom': 2.0, 'augment_shift': 1.0})
 for f in range(nfiles):
     with R.TFRecordWriter(os.path.join(tmp, '%d.tfrecords' % f)) as w:
         for i in range(per_file):
